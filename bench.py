@@ -363,6 +363,82 @@ def extra_schedules(eng, args, B, T, rank):
     return extra
 
 
+DUMP_BYTES = 64 << 20
+# The fixed state the dumped step starts from (--dump-outputs): a training state in mid-run, not the initial one.  From the initial
+# state (critic and LayerNorm biases 0, Adam moments 0) some outputs are pure rounding: the biases whose exact gradient vanishes hold
+# only the float atomics' residue after the step, and Adam's first update lr * g / (|g| + eps) = lr * sign(g) turns rounding in a
+# near-zero gradient into a whole lr-sized step (measured at cfg2: 2 lr in 442 of W_t's 98304 values between two identical runs).
+# Here every parameter is non-zero (synth.portable_state), the first / second moments are seeded per name (~1e-4 / ~1e-6 against
+# gradients of ~1e-4 .. 1e-3 after the 1.5-norm clip) and both optimizers are at step DUMP_ADAM_STEP: the update then depends
+# smoothly on the gradient (d update / d g = lr * 0.1 / sqrt(v_hat) ~ 0.1), so rounding in the gradient stays rounding in the outputs.
+DUMP_ADAM_STEP = 100
+
+
+def seeded_dump_state(eng, shapes):
+    """Device copies of the parameter and Adam-moment buckets of the fixed state above, generated by parameter NAME (the same in every
+    run and in every build, whatever the bucket layout); the engine is left in the state it had (bench's seeded initial state)."""
+    import zlib
+    m, v = {}, {}
+    for name, shape in shapes:
+        g = np.random.default_rng(zlib.crc32(("adam:" + name).encode()))
+        m[name] = (1e-4 * g.uniform(-1.0, 1.0, size=shape)).astype(np.float32)
+        v[name] = (1e-6 * g.uniform(0.5, 1.5, size=shape)).astype(np.float32)
+    eng.load_params(synth.portable_state(shapes, 0))
+    for group in ("main", "critic"):
+        eng.load_named_moments(group, m, v)
+    snap = {(b, k): bucket[k].clone() for b, bucket in (("main", eng.main), ("crit", eng.crit)) for k in "pmv"}
+    snap["counters"] = torch.tensor([0, DUMP_ADAM_STEP, DUMP_ADAM_STEP, 0], dtype=torch.int32, device=eng.counters.device)
+    eng.load_params(synth.default_state(shapes, 0))
+    for bucket in (eng.main, eng.crit):
+        bucket["m"].zero_()
+        bucket["v"].zero_()
+    torch.cuda.synchronize()
+    return snap
+
+
+def restore_dump_state(eng, snap):
+    """--dump-outputs, in front of the LAST timed step: the fixed state (seeded_dump_state) again, device-to-device on the engine's
+    stream, zero gradient buckets, the RNG step 0.  The steps before it carry the run-to-run rounding of float atomics, which Adam
+    amplifies step after step; from this state the dumped step's inputs are the same in every run and in every build.  ~110 MB of
+    device copies inside the timed region; the bf16 weight images are rebuilt by the step itself."""
+    for b, bucket in (("main", eng.main), ("crit", eng.crit)):
+        for k in "pmv":
+            bucket[k].copy_(snap[(b, k)])
+        bucket["g"].zero_()
+    eng.counters.copy_(snap["counters"])
+    eng.params_changed()
+
+
+def dump_outputs(eng, out_dir):
+    """What the last timed step hands its caller, as float32 DIR/<name>.npy: every parameter and both optimizers' Adam moments under
+    the reference's state_dict names (independent of the flat-bucket layout), the scalar block (losses, MI / CMI terms), the stage-2
+    predictions and features.  At most DUMP_BYTES in all: beyond that, arrays of more than 4096 values keep a fixed, seeded sample.
+    Float atomics make the default build differ run to run by rounding; MIMRL_DETERMINISTIC=1 is bit-identical."""
+    import zlib
+    torch.cuda.synchronize()
+    mom = eng.named_moments()
+    arrays = {"scalars": eng.scalars, "pred": eng.pred, "feats": eng.feats}
+    for name, p in eng.params.items():
+        group = "critic" if name in mom["critic"]["m"] else "main"
+        arrays["param." + name] = p
+        arrays["adam_m." + name] = mom[group]["m"][name]
+        arrays["adam_v." + name] = mom[group]["v"][name]
+    small = sum(4 * t.numel() + 128 for t in arrays.values() if t.numel() <= 4096)        # (+ 128: the .npy header)
+    large = sum(4 * t.numel() + 128 for t in arrays.values() if t.numel() > 4096)
+    keep = min(1.0, (DUMP_BYTES - small) / max(large, 1))
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if keep < 1.0 and a.size > 4096:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, int(a.size * keep), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    log(f"dumped {len(arrays)} arrays ({total / 1e6:.1f} MB) to {out_dir}")
+    return {"dir": os.path.abspath(out_dir), "arrays": len(arrays), "bytes": total, "sampled": keep < 1.0}
+
+
 def _descendants(pid):
     """PIDs of every live descendant of ``pid`` (/proc scan).  torchrun starts each rank in its OWN session, so killing the launcher's
     process group does not reach them: the watchdog kills exactly these PIDs -- children of the torchrun this launcher started."""
@@ -518,6 +594,9 @@ def main():
     ap.add_argument("--cpu-warmups", type=int, default=3, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-iters", type=int, default=20, help=argparse.SUPPRESS)
     ap.add_argument("--ddp-timeout", type=float, default=420.0, help="launcher mode (--gpus N without torchrun): watchdog per transport rung, seconds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32, "
+                    "at most 64 MB); the last timed step then starts from a fixed seeded state (seeded_dump_state), so the files are the "
+                    "same in every run up to rounding")
     args = ap.parse_args()
 
     if args.cpu_baseline_only:      # no GPU work in this child
@@ -551,6 +630,7 @@ def main():
                     seed=1234 + rank, device_anchors=True)
     shapes = [(n, tuple(v.shape)) for n, v in eng.params.items()]
     eng.load_params(synth.default_state(shapes, 0))                              # random init, identical on all ranks
+    dump_state = seeded_dump_state(eng, shapes) if args.dump_outputs else None
     eng.set_batch(*synth.synthetic_batch(B, T, seed=rank))                       # rank-local batch, resident in HBM
     banks = synth.synthetic_banks(N, seed=0)
     eng.set_banks(*(banks[k] for k in "CFTAV"))
@@ -647,7 +727,10 @@ def main():
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     e0.record()
-    for _ in range(args.steps):
+    for _ in range(args.steps - (1 if dump_state else 0)):
+        step()
+    if dump_state:                            # --dump-outputs: the last timed step starts from a fixed seeded state
+        restore_dump_state(eng, dump_state)
         step()
     e1.record()
     torch.cuda.synchronize()
@@ -672,6 +755,7 @@ def main():
                          "what": "sum over the int32 bit patterns of every parameter of the main / critic bucket, per rank, after the timed region"}
     wall = float(el.item())
     log(f"timed region: {1e3 * wall / args.steps:.3f} ms/step")
+    dumped = dump_outputs(eng, args.dump_outputs) if (args.dump_outputs and rank == 0) else None   # before the eager profile steps below
     stamps = eng.read_kernel_stamps() if use_stamps else {}
     if use_stamps:
         eng.lib.mimrl_set_kernel_stamps(eng.handle, None, 0)      # off for the eager phase profile below
@@ -906,6 +990,8 @@ def main():
             "roofline": roof, "kernels": kernels, "cpu_baseline": cpu, "phases": phases, "losses_finite": finite,
             "stage1_loss": float(scal[_lib.S1_LOSS]), "stage2_loss": float(scal[_lib.S2_LOSS]),
         }
+        if dumped:
+            out["dumped_outputs"] = dumped
         mdist.flush_c_stdio()          # (anything RCCL left in the C stdio buffer goes out BEFORE the line)
         print(json.dumps(out), flush=True)
     eng.close()
