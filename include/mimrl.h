@@ -37,6 +37,8 @@ enum { MIMRL_PREC_FP32 = 0, MIMRL_PREC_BF16_GEMM_FWD = 1, MIMRL_PREC_BF16_GEMM_B
 
 enum { MIMRL_BASELINE_CONSTANT = 0, MIMRL_BASELINE_GAUSSAIN = 1, MIMRL_BASELINE_UNNORMALIZED = 2 };   /* VMI.py:72-110 */
 enum { MIMRL_ENCODER_GRU = 0, MIMRL_ENCODER_CONV = 1, MIMRL_ENCODER_LSTM = 2 };    /* Model.py:247-257 */
+/* the stage-2 task loss (--loss, Solver.py:172-192): nn.L1Loss, nn.MSELoss, rmse (Utils.py:270), SIMSE (Utils.py:459), ccc_loss (Utils.py:22) */
+enum { MIMRL_TASK_LOSS_MAE = 0, MIMRL_TASK_LOSS_MSE = 1, MIMRL_TASK_LOSS_RMSE = 2, MIMRL_TASK_LOSS_SIMSE = 3, MIMRL_TASK_LOSS_CCC = 4 };
 
 /* Hot-path subset of Parameters.py:8-70 (same meaning as the flags of the same name). */
 typedef struct mimrl_cfg {
@@ -97,7 +99,7 @@ enum {
   MIMRL_S1_MIS = 1,       /* 11 values: mi_f_t..mi_t_v, cmi_ac_t..cmi_tc_v         */
   MIMRL_S1_LOSSES = 12,   /* 11 values: -mi x5, BCE x6                             */
   MIMRL_S2_LOSS = 32,     /* stage-2 total loss                                   */
-  MIMRL_S2_TASK = 33,     /* MAE task loss                                        */
+  MIMRL_S2_TASK = 33,     /* task loss, --loss                                    */
   MIMRL_S2_MIS = 34,      /* 8 values: f_t f_a f_v inv spec_t spec_a spec_v comp   */
   MIMRL_S2_LOSSES = 42,   /* 8 values                                             */
   MIMRL_NSCALARS = 64
@@ -203,6 +205,10 @@ int64_t mimrl_main_late_offset(const mimrl_handle* h);
  * gradients to bf16 once, RCCL sums in bf16, the sum is widened in front of clip + Adam -- two conversion launches inside the same graph.
  * Changes the update at the 2^-9 level of each gradient (Adam normalises the scale away); the main bucket stays fp32.  Default off. */
 int mimrl_set_comm_critic_bf16(mimrl_handle* h, int on);
+/* the task loss of every stage-2 step, forward and estimate of the handle (MIMRL_TASK_LOSS_*; default MAE).  Syncs the user stream; a
+ * change drops the captured graphs (the kind is fixed when a step is enqueued or captured).  The batch-coupled kinds (RMSE, SIMSE, CCC)
+ * are the loss of THIS handle's batch: under data parallelism they are not the loss of the joined batch.  Unknown kind: MIMRL_ERR_ARG. */
+int mimrl_set_task_loss(mimrl_handle* h, int kind);
 int mimrl_profile_read(mimrl_handle* h, float* ms_sum /*[MIMRL_NPHASES]*/, int32_t* launches /*[MIMRL_NPHASES]*/);  /* syncs; resets */
 /* GEMM family of the eager steps since the last read: out = {algorithmic FLOPs, algorithmic bytes (operands and output once),
  * summed launch durations in ms (HIP events on each launch's own stream), launches}; syncs; resets */
@@ -290,6 +296,9 @@ int mimrl_knn_r1_host(const float* z, int N, const int32_t* anchors, int m, int 
 int mimrl_set_knn_override_mask(mimrl_handle* h, int stage, unsigned call_mask);
 int mimrl_op_cmi_loss(void* stream, const float* logits, float* dlogits, float* bce, float* cmi, const float* g_bce,
                       const float* g_cmi, int E, int n, int hardtanh);
+/* task loss `kind` (MIMRL_TASK_LOSS_*) of pred[B] against y[B] into loss[0] and, unless dpred is NULL, dloss/dpred into dpred[B];
+ * one workgroup, 1 <= B <= 1024 */
+int mimrl_op_task_loss(void* stream, int kind, const float* pred, const float* y, float* dpred, float* loss, int B);
 /* fused ReLU-MLP stack (critic towers VMI.py:13-22, CMI classifier Model.py:47-72), bf16 MFMA, fp32 in/out.
  * W[l] is [dims[l+1], dims[l]] row-major, group g at + g*pstride (same for b[l], db[l]); activations are
  * [nb, brows, width].  forward: act[l] (l < nl-1) = post-ReLU outputs, out = linear top layer.

@@ -21,7 +21,7 @@ from . import _lib, dist as mdist, synth
 from .Customization import compute_custumized_loss, compute_outputs_from_model, other_model_operations
 from .engine import HipEngine
 from .Model import Model
-from .Utils import log_message, set_logger
+from .Utils import TASK_LOSS_FUNCTIONS, log_message, set_logger
 
 
 class _Plateau:
@@ -66,8 +66,7 @@ class Solver:
     def __init__(self, opt, loaders=None):
         self.opt = opt
         self.world, self.rank, self.local_rank = mdist.init_from_env()
-        if opt.loss != "MAE":
-            raise NotImplementedError(f"--loss {opt.loss}: only MAE is on the MI355X hot path (SURVEY.md section 2)")
+        _lib.task_loss_code(opt, self.world)      # --loss: the regression losses; classification and cross-rank batch coupling refused
         if opt.optm != "Adam":
             raise NotImplementedError(f"--optm {opt.optm}: only Adam is fused on the MI355X hot path")
         if torch.cuda.is_available():   # BEFORE the loaders: a resident dataset lands on the current device (data.py)
@@ -328,9 +327,10 @@ class Solver:
         return float(a[_lib.S2_LOSS]) / nb, mis, score, predictions, targets, feats
 
     def compute_loss(self, outputs, labels, stage, C_F_all, F_F_all, T_F_all, A_F_all, V_F_all):
-        """Solver.py:317-342 (MAE) -- losses evaluated on the features of the last forward."""
+        """Solver.py:317-342 (--loss: Utils.TASK_LOSS_FUNCTIONS) -- losses evaluated on the features of the last forward."""
         predictions = outputs[0]
-        task_loss = (predictions.reshape(-1) - torch.as_tensor(labels, device=predictions.device).reshape(-1)).abs().mean()
+        task_loss = TASK_LOSS_FUNCTIONS[self.opt.loss](predictions.reshape(-1),
+                                                       torch.as_tensor(labels, device=predictions.device).reshape(-1))
         return compute_custumized_loss(self.model, task_loss, outputs, labels, None, self.opt, stage, C_F_all, F_F_all,
                                        T_F_all, A_F_all, V_F_all)
 

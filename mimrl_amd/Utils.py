@@ -57,3 +57,30 @@ def set_logger(log_path: str):
 
 def log_message(message: str):
     logging.log(msg=message, level=logging.DEBUG)
+
+
+# --loss (Solver.py:172-192): the regression task losses, fp32 torch on the host (Solver.compute_loss); the device computes the same
+# (csrc/task_loss.h).  pred and y are flattened to [B] first (Solver.py:334-335).
+def rmse_loss(pred: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    return ((pred - y) ** 2).mean() ** 0.5
+
+
+def simse_loss(pred: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    n = y.numel()
+    return (y - pred).sum().pow(2) / (n * n)
+
+
+def ccc_loss(pred: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    mp, my = pred.mean(), y.mean()
+    cov = ((pred - mp) * (y - my)).mean()
+    vy, vp = ((y - my) ** 2).mean(), ((pred - mp) ** 2).mean()
+    return 1.0 - 2.0 * cov / (vy + vp + (my - mp) ** 2 + 1e-10)
+
+
+TASK_LOSS_FUNCTIONS = {
+    "MAE": lambda p, y: (p - y).abs().mean(),
+    "MSE": lambda p, y: ((p - y) ** 2).mean(),
+    "RMSE": rmse_loss,
+    "SIMSE": simse_loss,
+    "CCC": ccc_loss,
+}

@@ -101,6 +101,8 @@ def load() -> C.CDLL:
     lib.mimrl_comm_unique_id.argtypes = [_FP]
     lib.mimrl_set_comm.argtypes = [_FP, _FP, C.c_int, C.c_int]
     lib.mimrl_set_comm_critic_bf16.argtypes = [_FP, C.c_int]
+    lib.mimrl_set_task_loss.argtypes = [_FP, C.c_int]
+    lib.mimrl_op_task_loss.argtypes = [_FP, C.c_int, _FP, _FP, _FP, _FP, C.c_int]
     lib.mimrl_main_late_offset.argtypes = [_FP]
     lib.mimrl_main_late_offset.restype = C.c_int64
     lib.mimrl_op_gemm16.argtypes = [_FP, _FP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), _FP, _FP, C.c_int,
@@ -163,8 +165,28 @@ EXPORTS = [
     "mimrl_op_gru_saved_floats", "mimrl_op_gru_forward", "mimrl_op_gru_backward", "mimrl_op_gru_wgrad", "mimrl_op_concat_dw", "mimrl_op_mi_bound", "mimrl_op_mi_bound_ex", "mimrl_op_mi_bound_baseline", "mimrl_op_mi_sep_infonce", "mimrl_op_knn",
     "mimrl_op_cmi_loss", "mimrl_op_sample_anchors", "mimrl_knn_r1_host", "mimrl_set_knn_override_mask", "mimrl_op_mlp_stack_forward", "mimrl_op_mlp_stack_backward", "mimrl_op_adam",
     "mimrl_probe_cube", "mimrl_probe_mi", "mimrl_probe_cmi", "mimrl_probe_knn", "mimrl_probe_encoders", "mimrl_set_kernel_stamps", "mimrl_comm_unique_id", "mimrl_set_comm", "mimrl_main_late_offset", "mimrl_set_comm_critic_bf16",
-    "mimrl_stage1_pipe_prime", "mimrl_stage1_pipe",
+    "mimrl_stage1_pipe_prime", "mimrl_stage1_pipe", "mimrl_set_task_loss", "mimrl_op_task_loss",
 ]
+
+# --loss (Parameters.py:55, Solver.py:172-192) -> MIMRL_TASK_LOSS_*
+TASK_LOSSES = {"MAE": 0, "MSE": 1, "RMSE": 2, "SIMSE": 3, "CCC": 4}
+BATCH_COUPLED_LOSSES = ("RMSE", "SIMSE", "CCC")
+
+
+def task_loss_code(opt, world: int = 1) -> int:
+    """The engine's task-loss kind for ``opt.loss``.  The classification losses are refused, and so are the batch-coupled regression losses
+    under data parallelism: the reference (nn.DataParallel) evaluates them on the gathered global batch, and a mean of per-rank values is a
+    different loss.  MAE and MSE are means of per-row terms: exact under equal shards, the 1/world being folded into the update."""
+    loss = getattr(opt, "loss", "MAE")
+    if loss in ("Focal", "CE", "BCE"):
+        raise NotImplementedError(f"--loss {loss}: classification losses are not on the MI355X path (regression only: "
+                                  f"{', '.join(TASK_LOSSES)})")
+    if loss not in TASK_LOSSES:
+        raise NotImplementedError(f"--loss {loss}: unknown task loss (choose one of {', '.join(TASK_LOSSES)})")
+    if int(world) > 1 and loss in BATCH_COUPLED_LOSSES:
+        raise NotImplementedError(f"--loss {loss} couples the whole batch: with {int(world)} ranks each would see only its shard, not the "
+                                  f"reference's global batch; run it on one rank, or use MAE / MSE")
+    return TASK_LOSSES[loss]
 
 
 def check(rc: int) -> int:

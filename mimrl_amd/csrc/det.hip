@@ -105,7 +105,7 @@ bool det_launch_accumulates(const char* name) {
   }
   // kernels that never call acc_add (tests/test_layout.py::test_det_flush_rule_matches_the_sources checks this list against the sources)
   static const char* const kSafe[] = {"_fwd", "adam_kernel", "images_kernel", "bf16_image", "knn_", "sample_anchors", "seq_lengths", "l0_pack", "l0_unpack",
-                                      "text_post", "feat_mean", "tail_pre", "begin_stage", "mae_kernel", "finalize_stage", "stage_boundary",
+                                      "text_post", "feat_mean", "tail_pre", "begin_stage", "task_loss_kernel", "finalize_stage", "stage_boundary",
                                       "cmi_assemble", "copy_rows", "gather_sum4", "wt_transpose", "pad_rows", "mi_bound", "cmi_loss", "pair_expand",
                                       "pair_reduce", "gauss_baseline", "dbg_spin", "det_flush", "dropout_inplace", "add_inplace",
                                       "mi_sep_fused", "gemm_tall_kernel", "concat_ws_reduce"};

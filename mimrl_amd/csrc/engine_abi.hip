@@ -188,7 +188,7 @@ int mimrl_forward(mimrl_handle* h, int train_mode, int with_losses) {
   h->ev_next = 0;
   MX(h->model_forward(train_mode != 0, false));
   if (!with_losses) return MIMRL_OK;
-  launch_mae(h->stream, h->bufs.pred, h->bufs.labels, (float*)nullptr,
+  launch_task_loss(h->stream, h->task_loss, h->bufs.pred, h->bufs.labels, (float*)nullptr,
                      h->bufs.scalars + MIMRL_S2_TASK, h->cfg.batch);
   LAUNCH_CHECK();
   h->ev_next = 0;
@@ -213,7 +213,7 @@ int mimrl_estimate(mimrl_handle* h, int stage) {
     launch_finalize_stage1(h->stream, h->bufs.scalars, h->mi_raw, h->cmi_raw,
                        h->bce_raw, h->coef1());
   } else {
-    launch_mae(h->stream, h->bufs.pred, h->bufs.labels, (float*)nullptr,
+    launch_task_loss(h->stream, h->task_loss, h->bufs.pred, h->bufs.labels, (float*)nullptr,
                        h->bufs.scalars + MIMRL_S2_TASK, h->cfg.batch);
     launch_finalize_stage2(h->stream, h->bufs.scalars, h->mi_raw, h->cmi_raw,
                        h->coef2(), 1);
@@ -467,6 +467,16 @@ int mimrl_set_comm_critic_bf16(mimrl_handle* h, int on) {
   return MIMRL_OK;
 }
 
+int mimrl_set_task_loss(mimrl_handle* h, int kind) {
+  if (!h) return set_error(MIMRL_ERR_ARG, "null handle");
+  if (kind < MIMRL_TASK_LOSS_MAE || kind > MIMRL_TASK_LOSS_CCC) return set_error(MIMRL_ERR_ARG, "task loss kind %d unknown", kind);
+  if (kind == h->task_loss) return MIMRL_OK;
+  HIPX(hipStreamSynchronize(h->user_stream));
+  h->drop_graphs();
+  h->task_loss = kind;
+  return MIMRL_OK;
+}
+
 int64_t mimrl_main_late_offset(const mimrl_handle* h) { return h ? (int64_t)h->layout.late_offset : 0; }
 
 int mimrl_set_stage2_prefetch(mimrl_handle* h, int on) {
@@ -675,6 +685,15 @@ int mimrl_op_sample_anchors(void* stream, int32_t* anchors_out, int ncall, int m
 int mimrl_op_cmi_loss(void* stream, const float* logits, float* dlogits, float* bce, float* cmi, const float* g_bce,
                       const float* g_cmi, int E, int n, int hardtanh) {
   return cmi_loss_fwd_bwd(reinterpret_cast<hipStream_t>(stream), logits, dlogits, bce, cmi, g_bce, g_cmi, E, n, hardtanh);
+}
+
+int mimrl_op_task_loss(void* stream, int kind, const float* pred, const float* y, float* dpred, float* loss, int B) {
+  if (!pred || !y || !loss) return set_error(MIMRL_ERR_ARG, "task_loss: null argument");
+  if (kind < MIMRL_TASK_LOSS_MAE || kind > MIMRL_TASK_LOSS_CCC) return set_error(MIMRL_ERR_ARG, "task loss kind %d unknown", kind);
+  if (B < 1 || B > 1024) return set_error(MIMRL_ERR_ARG, "task_loss: batch %d outside [1, 1024]", B);
+  launch_task_loss(reinterpret_cast<hipStream_t>(stream), kind, pred, y, dpred, loss, B);
+  LAUNCH_CHECK();
+  return MIMRL_OK;
 }
 
 static int fill_mlp_args(MlpFusedArgs* fa, int nb, int rows, int brows, int nl, const int32_t* dims, const float* const* W,

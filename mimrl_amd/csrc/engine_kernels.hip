@@ -1,4 +1,4 @@
-// The step's own small kernels (see engine.h): stage bookkeeping, MAE, the two loss finalisers, the fused stage boundary.
+// The step's own small kernels (see engine.h): stage bookkeeping, the task loss, the two loss finalisers, the fused stage boundary.
 #include "engine.h"
 #include "stage_boundary.h"
 
@@ -14,18 +14,12 @@ __global__ void begin_stage_kernel(int* rng_step, int* adam_step, float* scalars
   for (int i = threadIdx.x; i < scal_n; i += blockDim.x) scalars[scal_off + i] = 0.f;
 }
 
-// MAE (nn.L1Loss, Solver.py:181-182) + its gradient
-__global__ void mae_kernel(const float* __restrict__ pred, const float* __restrict__ y, float* __restrict__ dpred,
-                           float* __restrict__ task, int B) {
+// the task loss (--loss, Solver.py:172-192; task_loss.h) + its gradient (dpred may be null)
+template <int KIND>
+__global__ void task_loss_kernel(const float* __restrict__ pred, const float* __restrict__ y, float* __restrict__ dpred,
+                                 float* __restrict__ task, int B) {
   __shared__ float red[16];
-  float s = 0.f;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    const float d = pred[b] - y[b];
-    s += fabsf(d);
-    if (dpred) dpred[b] = (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) / B;
-  }
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) *task = s / B;
+  task_loss_body<KIND, false>(pred, y, dpred, task, B, red);
 }
 
 // Model.py:341 + Customization.py:100-102
@@ -71,13 +65,14 @@ __global__ void finalize_stage2_kernel(float* scal, const float* mi, const float
   scal[MIMRL_S2_LOSS] = loss;
 }
 
-// Stage boundary of a combined two-stage step as ONE launch: finalize_stage1 (Model.py:341) + begin_stage(2) + MAE (Solver.py:181-182).
+// Stage boundary of a combined two-stage step as ONE launch: finalize_stage1 (Model.py:341) + begin_stage(2) + the task loss.
 // Behind the critic Adam; the stage-1 raw terms are still intact (stage 2's estimators overwrite them later).  (Body: stage_boundary.h --
 // by default it rides on the critic Adam launch instead, estimator_ops.hip: adam8_kernel.)
 static_assert(SB_NE_MI == NE_MI && SB_NE_CMI == NE_CMI, "stage_boundary.h restates the estimator counts");
+template <int KIND>
 __global__ void stage_boundary_kernel(StageBoundaryArgs a) {
   __shared__ float red[16];
-  stage_boundary_body(a, red);
+  stage_boundary_body<KIND>(a, red);
 }
 
 }  // namespace
@@ -108,8 +103,14 @@ void launch_bucket_from_bf16(hipStream_t s, const void* src, float* dst, long n)
 void launch_begin_stage(hipStream_t s, int* rng_step, int* adam_step, float* scalars, int scal_off, int scal_n) {
   hipLaunchKernelGGL(begin_stage_kernel, dim3(1), dim3(64), 0, s, rng_step, adam_step, scalars, scal_off, scal_n);
 }
-void launch_mae(hipStream_t s, const float* pred, const float* y, float* dpred, float* task, int B) {
-  hipLaunchKernelGGL(mae_kernel, dim3(1), dim3(256), 0, s, pred, y, dpred, task, B);
+void launch_task_loss(hipStream_t s, int kind, const float* pred, const float* y, float* dpred, float* task, int B) {
+  switch (kind) {
+    case MIMRL_TASK_LOSS_MSE: hipLaunchKernelGGL(task_loss_kernel<MIMRL_TASK_LOSS_MSE>, dim3(1), dim3(256), 0, s, pred, y, dpred, task, B); break;
+    case MIMRL_TASK_LOSS_RMSE: hipLaunchKernelGGL(task_loss_kernel<MIMRL_TASK_LOSS_RMSE>, dim3(1), dim3(256), 0, s, pred, y, dpred, task, B); break;
+    case MIMRL_TASK_LOSS_SIMSE: hipLaunchKernelGGL(task_loss_kernel<MIMRL_TASK_LOSS_SIMSE>, dim3(1), dim3(256), 0, s, pred, y, dpred, task, B); break;
+    case MIMRL_TASK_LOSS_CCC: hipLaunchKernelGGL(task_loss_kernel<MIMRL_TASK_LOSS_CCC>, dim3(1), dim3(256), 0, s, pred, y, dpred, task, B); break;
+    default: hipLaunchKernelGGL(task_loss_kernel<MIMRL_TASK_LOSS_MAE>, dim3(1), dim3(256), 0, s, pred, y, dpred, task, B); break;
+  }
 }
 void launch_finalize_stage1(hipStream_t s, float* scal, const float* mi, const float* cmi, const float* bce, const float* coef1) {
   hipLaunchKernelGGL(finalize_stage1_kernel, dim3(1), dim3(64), 0, s, scal, mi, cmi, bce, coef1);
@@ -118,8 +119,15 @@ void launch_finalize_stage2(hipStream_t s, float* scal, const float* mi, const f
   hipLaunchKernelGGL(finalize_stage2_kernel, dim3(1), dim3(64), 0, s, scal, mi, cmi, coef2, have_mi);
 }
 void launch_stage_boundary(hipStream_t s, float* scal, const float* mi, const float* cmi, const float* bce, const float* coef1, int* rng_step,
-                           int* adam_step, const float* pred, const float* y, float* dpred, int B) {
-  hipLaunchKernelGGL(stage_boundary_kernel, dim3(1), dim3(256), 0, s, StageBoundaryArgs{scal, mi, cmi, bce, coef1, rng_step, adam_step, pred, y, dpred, B});
+                           int* adam_step, const float* pred, const float* y, float* dpred, int B, int kind) {
+  const StageBoundaryArgs a{scal, mi, cmi, bce, coef1, rng_step, adam_step, pred, y, dpred, B};
+  switch (kind) {
+    case MIMRL_TASK_LOSS_MSE: hipLaunchKernelGGL(stage_boundary_kernel<MIMRL_TASK_LOSS_MSE>, dim3(1), dim3(256), 0, s, a); break;
+    case MIMRL_TASK_LOSS_RMSE: hipLaunchKernelGGL(stage_boundary_kernel<MIMRL_TASK_LOSS_RMSE>, dim3(1), dim3(256), 0, s, a); break;
+    case MIMRL_TASK_LOSS_SIMSE: hipLaunchKernelGGL(stage_boundary_kernel<MIMRL_TASK_LOSS_SIMSE>, dim3(1), dim3(256), 0, s, a); break;
+    case MIMRL_TASK_LOSS_CCC: hipLaunchKernelGGL(stage_boundary_kernel<MIMRL_TASK_LOSS_CCC>, dim3(1), dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL(stage_boundary_kernel<MIMRL_TASK_LOSS_MAE>, dim3(1), dim3(256), 0, s, a); break;
+  }
 }
 
 }  // namespace eng

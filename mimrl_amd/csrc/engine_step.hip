@@ -131,7 +131,7 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
   if (fuse_boundary) {
     if (!boundary_in_adam)   // (else: workgroup 0 of the critic Adam launch did it -- enqueue_apply)
       launch_stage_boundary(stream, bufs.scalars, mi_raw, cmi_raw, bce_raw, coef1(), d_ints, d_ints + 1,
-                         bufs.pred, bufs.labels, dpred, B);
+                         bufs.pred, bufs.labels, dpred, B, task_loss);
     boundary_in_adam = false;
   } else {
     launch_begin_stage(stream, d_ints, d_ints + 1, bufs.scalars, 32, 32);
@@ -145,7 +145,7 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
     MX(model_forward(true, true, have_banks ? 2 : 0));
   }
   if (!fuse_boundary) {
-    launch_mae(stream, bufs.pred, bufs.labels, dpred, bufs.scalars + MIMRL_S2_TASK, B);
+    launch_task_loss(stream, task_loss, bufs.pred, bufs.labels, dpred, bufs.scalars + MIMRL_S2_TASK, B);
     LAUNCH_CHECK();
   }
   if (have_banks) {
@@ -222,7 +222,7 @@ int mimrl_handle::enqueue_apply(int stage) {
     a.sb = StageBoundaryArgs{bufs.scalars, mi_raw, cmi_raw, bce_raw, coef1(), d_ints, d_ints + 1, bufs.pred, bufs.labels, dpred, cfg.batch};
     boundary_in_adam = true;
   }
-  MX(adam_step(stream, a));
+  MX(adam_step(stream, a, task_loss));
   if (have_frag) {
     // combined step: beside the stage boundary on side 3 (the stage-2 estimators join it before their first stack)
     constexpr bool inline_frag = false;   // (an environment knob until round 5: fixed at its measured optimum)

@@ -112,7 +112,8 @@ struct AdamArgs {
   int sb_on = 0;
   StageBoundaryArgs sb;
 };
-int adam_step(hipStream_t s, const AdamArgs& a);
+// sb_kind: the task loss of the stage boundary when a.sb_on (MIMRL_TASK_LOSS_*), chooses the adam8_kernel instantiation
+int adam_step(hipStream_t s, const AdamArgs& a, int sb_kind = MIMRL_TASK_LOSS_MAE);
 
 #ifdef MIMRL_PHASE_PROBE
 int nce_read_phases(long long* out);   // 8 ticks, see estimator_ops.hip

@@ -774,10 +774,12 @@ __global__ void adam_kernel(AdamArgs a) {
 }
 
 // The same update, 8 consecutive elements per thread (two 16-byte pieces per array), for buckets without parked pieces (AdamArgs::Frag,
-// ::sb): same per-element arithmetic as adam_kernel, so parameters and moments are bit-identical to it.
+// ::sb): same per-element arithmetic as adam_kernel, so parameters and moments are bit-identical to it.  KIND: the task loss of the stage
+// boundary (adam_step's sb_kind; MAE when sb_on is 0).
+template <int KIND>
 __global__ __launch_bounds__(256) void adam8_kernel(AdamArgs a) {
   __shared__ float red[16];
-  if (a.sb_on && blockIdx.x == 0) stage_boundary_body(a.sb, red);
+  if (a.sb_on && blockIdx.x == 0) stage_boundary_body<KIND>(a.sb, red);
   const int t = *a.step;
   const float lr = *a.lr;
   const float bc1 = 1.f - powf(a.beta1, (float)t), bc2 = 1.f - powf(a.beta2, (float)t);
@@ -939,10 +941,17 @@ int top1_bwd(hipStream_t s, const float* dout, const float* W, const float* act,
   return MIMRL_OK;
 }
 
-int adam_step(hipStream_t s, const AdamArgs& a) {
+int adam_step(hipStream_t s, const AdamArgs& a, int sb_kind) {
   if (a.frag.n > 0 || a.sb_on) {
     if (a.n % 8 != 0 || a.fold.n != 0 || a.frag.n > 12 || (a.frag.n > 0 && a.n >= (1L << 24))) return set_error(MIMRL_ERR_ARG, "adam_step: the 8-wide kernel needs n %% 8 == 0, no parked pieces, <= 12 image entries");
-    hipLaunchKernelGGL(adam8_kernel, dim3(grid_for(a.n / 8, 256, 2048)), dim3(256), 0, s, a);
+    const dim3 grid(grid_for(a.n / 8, 256, 2048));
+    switch (a.sb_on ? sb_kind : MIMRL_TASK_LOSS_MAE) {
+      case MIMRL_TASK_LOSS_MSE: hipLaunchKernelGGL(adam8_kernel<MIMRL_TASK_LOSS_MSE>, grid, dim3(256), 0, s, a); break;
+      case MIMRL_TASK_LOSS_RMSE: hipLaunchKernelGGL(adam8_kernel<MIMRL_TASK_LOSS_RMSE>, grid, dim3(256), 0, s, a); break;
+      case MIMRL_TASK_LOSS_SIMSE: hipLaunchKernelGGL(adam8_kernel<MIMRL_TASK_LOSS_SIMSE>, grid, dim3(256), 0, s, a); break;
+      case MIMRL_TASK_LOSS_CCC: hipLaunchKernelGGL(adam8_kernel<MIMRL_TASK_LOSS_CCC>, grid, dim3(256), 0, s, a); break;
+      default: hipLaunchKernelGGL(adam8_kernel<MIMRL_TASK_LOSS_MAE>, grid, dim3(256), 0, s, a); break;
+    }
     LAUNCH_CHECK();
     return MIMRL_OK;
   }

@@ -1,9 +1,10 @@
-// The stage boundary of a combined two-stage step (finalize_stage1, Model.py:341 + Customization.py:100-102; begin_stage(2); MAE,
-// Solver.py:181-182) as a device function: its own one-workgroup launch (engine_kernels.hip: stage_boundary_kernel) or, round 5b, the
+// The stage boundary of a combined two-stage step (finalize_stage1, Model.py:341 + Customization.py:100-102; begin_stage(2); the task
+// loss, Solver.py:172-192 --loss: task_loss.h) as a device function: its own one-workgroup launch (engine_kernels.hip: stage_boundary_kernel) or, round 5b, the
 // first thing workgroup 0 of the critic clip + Adam launch does (estimator_ops.hip: adam8_kernel) -- one launch and one dependent-launch
 // gap less between the stage-1 critic update and the stage-2 estimators.
 #pragma once
 #include "common.h"
+#include "task_loss.h"
 
 namespace mimrl {
 
@@ -15,7 +16,8 @@ struct StageBoundaryArgs {
   const float *pred, *y; float* dpred; int B;
 };
 
-// all threads of ONE workgroup (blockDim.x a multiple of 64, <= 1024); `red`: 16 floats of LDS
+// all threads of ONE workgroup (blockDim.x a multiple of 64, <= 1024); `red`: 16 floats of LDS; KIND: the task loss (MIMRL_TASK_LOSS_*)
+template <int KIND>
 __device__ __forceinline__ void stage_boundary_body(const StageBoundaryArgs& a, float* red) {
   if (threadIdx.x == 0) {
     // every value is READ before the first store (tools/isa_lint.py: interleaved with the stores into `scal`, which may alias, these were
@@ -44,15 +46,7 @@ __device__ __forceinline__ void stage_boundary_body(const StageBoundaryArgs& a, 
     *a.adam_step = as + 1;
   }
   for (int i = threadIdx.x; i < 32; i += blockDim.x) a.scal[32 + i] = 0.f;
-  float s = 0.f;
-  for (int b = threadIdx.x; b < a.B; b += blockDim.x) {
-    const float d = a.pred[b] - a.y[b];
-    s += fabsf(d);
-    a.dpred[b] = (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) / a.B;
-  }
-  s = block_sum(s, red);
-  __syncthreads();                       // the zeroing of scal[32..63] above is complete before the task loss lands in it
-  if (threadIdx.x == 0) a.scal[MIMRL_S2_TASK] = s / a.B;
+  task_loss_body<KIND, true>(a.pred, a.y, a.dpred, a.scal + MIMRL_S2_TASK, a.B, red);   // (behind the zeroing of scal[32..63] above)
 }
 
 }  // namespace mimrl

@@ -84,6 +84,11 @@ class HipEngine:
         check(self.lib.mimrl_create(C.byref(self.cfg), C.c_void_p(self.stream.cuda_stream), C.byref(h)))
         self.handle = h
         self._bind()
+        # --loss: the handle starts at MAE; a sibling handle (``share``) keeps the loss of the engine whose optimizer it shares
+        self.task_loss = _lib.TASK_LOSSES["MAE"]
+        kind = share.task_loss if share is not None else _lib.task_loss_code(opt)
+        if kind != self.task_loss:
+            self.set_task_loss(kind)
 
     def _bind(self):
         b = Buffers()
@@ -271,10 +276,22 @@ class HipEngine:
             check(self.lib.mimrl_set_comm(self.handle, None, 1, 0))
             self.comm_world = 0
             return
+        if int(world) > 1 and self.task_loss not in (_lib.TASK_LOSSES["MAE"], _lib.TASK_LOSSES["MSE"]):
+            raise NotImplementedError("a batch-coupled task loss (RMSE, SIMSE, CCC) is the loss of the whole batch, not of one rank's shard: "
+                                      "single rank only")
         buf = (C.c_char * 128).from_buffer_copy(bytes(unique_id))
         check(self.lib.mimrl_set_comm(self.handle, C.cast(buf, C.c_void_p), int(world), int(rank)))
         self.comm_world = int(world)
         self.set_grad_scale(1.0 / world)
+
+    def set_task_loss(self, kind: int):
+        """The stage-2 task loss of this handle (include/mimrl.h: mimrl_set_task_loss; ``_lib.TASK_LOSSES``): every later step, forward
+        and estimate.  Syncs; a change drops the captured graphs."""
+        self._coherent()
+        if getattr(self, "comm_world", 0) > 1 and kind not in (_lib.TASK_LOSSES["MAE"], _lib.TASK_LOSSES["MSE"]):
+            raise NotImplementedError("a batch-coupled task loss (RMSE, SIMSE, CCC) needs the whole batch on one rank")
+        check(self.lib.mimrl_set_task_loss(self.handle, int(kind)))
+        self.task_loss = int(kind)
 
     def set_comm_critic_bf16(self, on: bool):
         """The critic bucket's all-reduce in bf16 (include/mimrl.h: mimrl_set_comm_critic_bf16): half the bytes of the larger collective."""
