@@ -10,6 +10,11 @@ k-NN CMI with k=2 against N=1284-row banks, Adam lr 4e-3, clip 1.5, dropout 0.1)
 Inputs are resident in HBM before the timed region; every step runs the full forward, all 11 estimators, the
 backward and the fused clip+Adam of both stages, kNN anchor sampling included (on the device).
 Rank 0 prints ONE JSON line.
+
+A plain run measures the headline only: set-up, warm-up, the timed steps, --dump-outputs, the line (with the roofline of the
+recurrence backward from the in-graph launch stamps of the timed region).  --full adds every figure that takes runs of its own:
+the other schedules and the fp32 parity mode (child process), cfg3 and the deterministic build (child processes), the eager
+per-phase / per-kernel profile and the CPU-oracle baseline; --no-extra, --no-cpu-baseline and --profile-steps 0 leave parts out.
 """
 import argparse
 import json
@@ -581,10 +586,13 @@ def main():
     ap.add_argument("--workload", default="cfg2")
     ap.add_argument("--precision", default="bf16", choices=sorted(_lib.PREC))
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the other schedules, cfg3 and the "
+                    "deterministic build (child processes), the eager per-phase / per-kernel profile, the CPU-oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
     ap.add_argument("--no-prefetch", action="store_true", help="run the two stages strictly one after the other")
-    ap.add_argument("--profile-steps", type=int, default=20)
-    ap.add_argument("--no-extra", action="store_true", help="skip the sequential / fresh-batch schedules")
+    ap.add_argument("--profile-steps", type=int, default=20, help="with --full: eager steps of the per-phase profile (0: none)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the child processes (other schedules, cfg3, "
+                    "deterministic build)")
     ap.add_argument("--prewarm-ms", type=float, default=300.0, help="untimed steps in FRONT of the --warmup steps until this much wall time "
                     "has passed: a fresh process starts with idle clocks and cold caches, and the driver's 5 + 20 steps are 25 ms in all")
     ap.add_argument("--extras-only", action="store_true", help=argparse.SUPPRESS)   # child mode: print only the extra schedules
@@ -764,9 +772,9 @@ def main():
 
     # ---- the other schedules of the same step -- strictly sequential stages (what Solver.train's epoch-ordered passes get per
     #      stage pair) and fresh host batches through the overlapped upload path (PCIe-inclusive) -- measured in a CHILD process
-    #      (same workload, its own engine) so that nothing in these optional figures can take the headline measurement down
+    #      (same workload, its own engine) so that nothing in these optional figures can take the headline measurement down (--full)
     extra = {}
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), "--extras-only", "--workload", args.workload, "--precision", args.precision,
                "--steps", str(args.steps)] + (["--no-graph"] if args.no_graph else []) + (["--no-prefetch"] if args.no_prefetch else [])
@@ -804,9 +812,9 @@ def main():
                 extra["deterministic_build"] = {"error": repr(e)[:200]}
             log(f"deterministic build (child process): {extra['deterministic_build']}")
 
-    # ---- live per-phase and GEMM-family timing with HIP events on the launch streams (eager launches)
+    # ---- live per-phase and GEMM-family timing with HIP events on the launch streams (eager launches; --full)
     phases, roof, kernels = {}, None, []
-    if rank == 0 and args.profile_steps > 0:
+    if rank == 0 and args.full and args.profile_steps > 0:
         if world > 1:
             eng.set_stage2_prefetch(False)   # the lone stage calls below are the sequential schedule (deferred-tail mode refuses them)
         eng.profile(True)
@@ -949,7 +957,7 @@ def main():
                            "achieved_gbs": bwd_by / (avg_us * 1e-6) / 1e9, "note": f"{avg_us / T:.3f} us per dependent cell step"})
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.workload)
 
     if rank == 0:
@@ -975,7 +983,7 @@ def main():
                                          "recurrence, the estimators and every backward product; fp32 accumulate, state, statistics and optimizer"
                                          if _lib.PREC[args.precision] else "fp32 MFMA operands (v_mfma_f32_*_f32), fp32 everywhere"),
                        "hipgraph": not args.no_graph, "stage2_forward_overlap": not args.no_prefetch and not _lib.DETERMINISTIC,
-                       "deterministic_build": bool(_lib.DETERMINISTIC),
+                       "deterministic_build": bool(_lib.DETERMINISTIC), "full": args.full,
                        "shared_encoder_prefix": (not args.no_prefetch) and not os.environ.get("MIMRL_NO_SHARED_PREFIX"), "samples_per_sec": B * world * args.steps / wall},
             "algorithmic_gflop_per_step": algorithmic_flops(opt, N) / 1e9,
             "achieved_tflops_whole_step": world * algorithmic_flops(opt, N) / (wall / args.steps) / 1e12,

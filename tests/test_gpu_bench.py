@@ -48,6 +48,23 @@ def test_bench_dump_outputs_are_bit_identical_in_the_deterministic_build(tmp_pat
 
 
 @pytest.mark.gpu
+def test_plain_run_measures_the_headline_only():
+    """Without --full the run starts no child process, no eager profile and no CPU baseline: the line carries the headline and the
+    roofline of the timed region's launch stamps, none of the figures --full adds."""
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    env.pop("MIMRL_DETERMINISTIC", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2"], env=env, capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["config"]["full"] is False and d["steps"] == 10 and d["losses_finite"]
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["cpu_baseline"] is None and d["phases"] == {}
+    assert not {"ms_per_step_sequential", "ms_per_step_fresh_batch", "cfg3", "deterministic_build", "extras_error"} & set(d)
+    assert d["roofline"]["launches_timed"] == 2 * 10
+
+
+@pytest.mark.gpu
 def test_bench_dump_outputs_agree_to_rounding_in_the_default_build(tmp_path):
     """The timed build (float atomics): two runs agree to rounding in every dumped array, measured against the array's own scale
     (measured at most 1e-6; from the initial state, where some outputs are pure rounding residue and Adam's first step is lr * sign(g),
