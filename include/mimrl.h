@@ -24,6 +24,10 @@ extern "C" {
 
 #define MIMRL_ABI_VERSION 6
 #define MIMRL_MAX_BLOCKS 4
+/* per-rank batch ceiling of mimrl_create (mimrl_cfg.batch); the concat critic keeps 1024: its pair activations are
+ * 6 x 5 x B^2 x 256 floats (32 GiB at B = 1024, 129 GiB at B = 2048) */
+#define MIMRL_MAX_BATCH 2048
+#define MIMRL_MAX_BATCH_CONCAT 1024
 
 enum { MIMRL_OK = 0, MIMRL_ERR_ARG = -1, MIMRL_ERR_HIP = -2, MIMRL_ERR_STATE = -3, MIMRL_ERR_NODEVICE = -4 };
 enum { MIMRL_GROUP_MAIN = 0, MIMRL_GROUP_CRITIC = 1 };
@@ -42,7 +46,7 @@ enum { MIMRL_TASK_LOSS_MAE = 0, MIMRL_TASK_LOSS_MSE = 1, MIMRL_TASK_LOSS_RMSE = 
 
 /* Hot-path subset of Parameters.py:8-70 (same meaning as the flags of the same name). */
 typedef struct mimrl_cfg {
-  int32_t batch;                 /* --batch_size (rows per rank) */
+  int32_t batch;                 /* --batch_size (rows per rank), 1 .. MIMRL_MAX_BATCH (concat critic: MIMRL_MAX_BATCH_CONCAT) */
   int32_t seq_len;               /* T of the input triples, <= time_len */
   int32_t time_len;              /* --time_len (L axis of CubeMLP) */
   int32_t d_t, d_a, d_v;         /* 768 / 74 / 35 for MOSI-shaped data (Config.py:59-76) */
@@ -270,6 +274,12 @@ int mimrl_op_mi_bound(void* stream, const float* scores, float* dscores, float* 
  * estimator e enters the objective through its loss term (all in stage 1; f_t,f_a,f_v in stage 2, Model.py:386) */
 int mimrl_op_mi_bound_ex(void* stream, const float* scores, float* dscores, float* mi, float* mi_loss, const float* gscale,
                          int E, int B, int bound, uint32_t lossform);
+/* InfoNCE through the engine's row-tiled kernel (one wave per score row, an ordered sum of per-workgroup slots): the same outputs as
+ * mimrl_op_mi_bound_ex with MIMRL_BOUND_INFONCE.  E <= 16, 1 <= B <= MIMRL_MAX_BATCH.  ws: MIMRL_NCE_WS_FLOATS device floats, zero before
+ * the first call; every call resets the ticket counters it used (not shared by two calls in flight) */
+#define MIMRL_NCE_WS_FLOATS 2064
+int mimrl_op_mi_infonce_rows(void* stream, const float* scores, float* dscores, float* mi, float* mi_loss, const float* gscale,
+                             int E, int B, float* ws);
 /* tuba / interpolate with a log-baseline log a(y_i) per row (VMI.py:72-110): lb, dlb are [E,B]; scores are modified in place */
 int mimrl_op_mi_bound_baseline(void* stream, float* scores, float* dscores, float* mi, const float* gscale, const float* lb,
                                float* dlb, int E, int B, int bound);

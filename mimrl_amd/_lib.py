@@ -14,6 +14,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DETERMINISTIC = os.environ.get("MIMRL_DETERMINISTIC", "0") not in ("", "0")
 LIB_PATH = os.environ.get("MIMRL_LIB_PATH") or os.path.join(_HERE, "libmimrl_hip_det.so" if DETERMINISTIC else "libmimrl_hip.so")
 MAX_BLOCKS = 4
+MAX_BATCH = 2048            # MIMRL_MAX_BATCH: rows per rank
+MAX_BATCH_CONCAT = 1024     # MIMRL_MAX_BATCH_CONCAT: rows per rank with the concat critic
+NCE_WS_FLOATS = 2064        # MIMRL_NCE_WS_FLOATS: workspace of mimrl_op_mi_infonce_rows
 NSCALARS = 64
 PHASES = ["gemm_misc", "gru_fwd", "gru_bwd", "cube_fwd", "cube_bwd", "est_fwd", "est_bwd", "opt", "model_misc"]
 S1_LOSS, S1_MIS, S1_LOSSES, S2_LOSS, S2_TASK, S2_MIS, S2_LOSSES = 0, 1, 12, 32, 33, 34, 42
@@ -117,6 +120,7 @@ def load() -> C.CDLL:
     lib.mimrl_op_gru_wgrad.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5 + [C.c_int64, C.c_int]
     lib.mimrl_op_mi_bound.argtypes = [_FP] * 5 + [C.c_int, C.c_int, C.c_int]
     lib.mimrl_op_mi_bound_ex.argtypes = [_FP] * 6 + [C.c_int, C.c_int, C.c_int, C.c_uint32]
+    lib.mimrl_op_mi_infonce_rows.argtypes = [_FP] * 6 + [C.c_int, C.c_int, _FP]
     lib.mimrl_op_mi_sep_infonce.argtypes = [_FP] * 6 + [C.c_int, C.c_int, C.c_int]
     lib.mimrl_op_mi_bound_baseline.argtypes = [_FP] * 7 + [C.c_int, C.c_int, C.c_int]
     lib.mimrl_op_knn.argtypes = [_FP, _FP, C.c_int, C.c_int, _FP, C.c_int, C.c_int, _FP]
@@ -166,6 +170,7 @@ EXPORTS = [
     "mimrl_op_cmi_loss", "mimrl_op_sample_anchors", "mimrl_knn_r1_host", "mimrl_set_knn_override_mask", "mimrl_op_mlp_stack_forward", "mimrl_op_mlp_stack_backward", "mimrl_op_adam",
     "mimrl_probe_cube", "mimrl_probe_mi", "mimrl_probe_cmi", "mimrl_probe_knn", "mimrl_probe_encoders", "mimrl_set_kernel_stamps", "mimrl_comm_unique_id", "mimrl_set_comm", "mimrl_main_late_offset", "mimrl_set_comm_critic_bf16",
     "mimrl_stage1_pipe_prime", "mimrl_stage1_pipe", "mimrl_set_task_loss", "mimrl_op_task_loss",
+    "mimrl_op_mi_infonce_rows",
 ]
 
 # --loss (Parameters.py:55, Solver.py:172-192) -> MIMRL_TASK_LOSS_*

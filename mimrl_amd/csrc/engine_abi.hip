@@ -32,7 +32,11 @@ int mimrl_create(const mimrl_cfg* cfg, void* hip_stream, mimrl_handle** out) {
   if (!cfg || !out) return set_error(MIMRL_ERR_ARG, "null argument");
   *out = nullptr;
   MX(validate_cfg(*cfg));
-  if (cfg->batch > 1024) return set_error(MIMRL_ERR_ARG, "batch per rank must be <= 1024");
+  if (cfg->batch > MIMRL_MAX_BATCH)
+    return set_error(MIMRL_ERR_ARG, "batch per rank %d exceeds MIMRL_MAX_BATCH (%d)", cfg->batch, MIMRL_MAX_BATCH);
+  if (cfg->critic_type == MIMRL_CRITIC_CONCAT && cfg->batch > MIMRL_MAX_BATCH_CONCAT)
+    return set_error(MIMRL_ERR_ARG, "batch per rank %d exceeds MIMRL_MAX_BATCH_CONCAT (%d): the concat critic's pair activations "
+                     "grow as B^2 (6 x 5 x B^2 x 256 floats)", cfg->batch, MIMRL_MAX_BATCH_CONCAT);
 #ifndef MIMRL_DEBUG_KNOBS
   // result-changing debug knobs do not exist in this build; a run that sets one expects something this library will not do
   for (int i = 0; kDebugKnobs[i]; ++i)
@@ -651,6 +655,13 @@ int mimrl_op_mi_bound_ex(void* stream, const float* scores, float* dscores, floa
   return mi_bound_fwd_bwd(reinterpret_cast<hipStream_t>(stream), scores, dscores, mi, mi_loss, gscale, E, B, bound, lossform);
 }
 
+int mimrl_op_mi_infonce_rows(void* stream, const float* scores, float* dscores, float* mi, float* mi_loss, const float* gscale,
+                             int E, int B, float* ws) {
+  static_assert(MIMRL_NCE_WS_FLOATS >= NCE_WS_WIDE_FLOATS && NCE_WS_WIDE_FLOATS >= NCE_WS_FLOATS, "MIMRL_NCE_WS_FLOATS too small");
+  if (!scores || !mi || !ws || E < 1 || E > 16) return set_error(MIMRL_ERR_ARG, "mi_infonce_rows: null array or E = %d outside [1, 16]", E);
+  return mi_bound_fwd_bwd(reinterpret_cast<hipStream_t>(stream), scores, dscores, mi, mi_loss, gscale, E, B, BOUND_INFONCE, 0u, nullptr,
+                          nullptr, 0, ws);
+}
 int mimrl_op_mi_sep_infonce(void* stream, const float* tout, float* dtout, float* mi, float* mi_loss, const float* gscale, int E,
                             int B, int tiled) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);

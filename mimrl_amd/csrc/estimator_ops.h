@@ -23,9 +23,12 @@ bool mi_sep_fused_supported(int B);
 int mi_sep_nce_tiled(hipStream_t s, const float* tout, float* dtout, float* mi, float* mil, const float* gscale, int E, int B, int do_bwd);
 int mi_sep_fused(hipStream_t s, const float* tout, float* dtout, float* mi, float* mil, const float* gscale, int E, int B,
                  int bound, unsigned lossform, int do_bwd, const float* lb = nullptr, float* dlb = nullptr, long lb_stride = 0);
-// `nce_ws`: NCE_WS_FLOATS zero-initialised floats owned by the caller (one per engine handle): ticket + slots of the row-tiled InfoNCE kernel;
-// nullptr = the one-workgroup-per-estimator kernel, which shares no state between launches
+// `nce_ws`: nce_ws_floats(B) zero-initialised floats owned by the caller (one per engine handle): ticket + slots of the row-tiled InfoNCE
+// kernel; nullptr = the one-workgroup-per-estimator kernel, which shares no state between launches.  B <= 1024: 64 slots per estimator;
+// 1024 < B <= MIMRL_MAX_BATCH: the wide kernel's 128 (B / 16 workgroups of 16 rows each).
 constexpr int NCE_WS_FLOATS = 16 + 16 * 64;
+constexpr int NCE_WS_WIDE_FLOATS = 16 + 16 * 128;
+inline int nce_ws_floats(int B) { return B > 1024 ? NCE_WS_WIDE_FLOATS : NCE_WS_FLOATS; }
 int mi_bound_fwd_bwd(hipStream_t s, const float* scores, float* dscores, float* mi, float* mil, const float* gscale, int E,
                      int B, int bound, unsigned lossform, const float* lb = nullptr, float* dlb = nullptr, long lb_stride = 0,
                      float* nce_ws = nullptr);

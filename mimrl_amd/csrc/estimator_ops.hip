@@ -233,18 +233,37 @@ __global__ __launch_bounds__(1024) void mi_bound_kernel(const float* scores, flo
                 dlb ? dlb + e * lb_stride : nullptr);
 }
 
+// The same for 1024 < B <= MIMRL_MAX_BATCH (launched only there, so the kernel above stays as it was for smaller batches): the six
+// per-row statistics vectors no longer fit the static array and live in 6 B floats of dynamic LDS (48 KiB at B = 2048).
+__global__ __launch_bounds__(1024) void mi_bound_wide_kernel(const float* scores, float* dscores,
+                                                             float* __restrict__ mi, float* __restrict__ mil,
+                                                             const float* __restrict__ gscale, int B, int bound, unsigned lossform,
+                                                             const float* __restrict__ lb, float* __restrict__ dlb, long lb_stride) {
+  __shared__ float red[16];
+  extern __shared__ float rowstat_dyn[];   // [6 * B]
+  const int e = blockIdx.x;
+  mi_bound_body(const_cast<float*>(scores) + (long)e * B * B, dscores ? dscores + (long)e * B * B : nullptr, mi, mil,
+                gscale ? gscale[e] : 0.f, e, B, bound, lossform, red, rowstat_dyn, lb ? lb + e * lb_stride : nullptr,
+                dlb ? dlb + e * lb_stride : nullptr);
+}
+
 // InfoNCE on score matrices that live in memory (the concat critic; round 5): the bound is ROW-wise -- mi = log B + mean_i(s_ii - lse_i),
 // dS_ij = gs / B ((i == j) - e^{s_ij - lse_i}) (VMI.py:162-166) -- so one wave per row, 16 rows per workgroup, B / 16 workgroups per
 // estimator instead of ONE: mi_bound_kernel walked each 256 x 256 matrix of cfg3 with a single workgroup (5 CUs busy, 68 + 49 us on the
 // chain of the two stages).  The row sums of a workgroup go to a slot, the last workgroup of an estimator (ticket) adds the slots in order:
-// the value does not depend on arrival order.  B <= 1024 (a row in registers: 16 values per lane).
+// the value does not depend on arrival order.  A row sits in registers, NV values per lane: NV = 16 for B <= 1024 (64 slots per
+// estimator, NceWs), NV = 32 for 1024 < B <= 2048 (128 slots, NceWsWide; launched only there).
 // Ticket counters and slots live in a CALLER-owned workspace (NceWs: zeroed once, self-resetting) -- per engine handle, so that two handles
 // on different streams (or an op-level call beside a step) never share a ticket (round 5 kept them in process-global arrays).
 constexpr int NCE_MAX_EST = 16;
-struct NceWs { unsigned ticket[NCE_MAX_EST]; float part[NCE_MAX_EST][64]; };
+template <int NSLOT> struct NceWsT { unsigned ticket[NCE_MAX_EST]; float part[NCE_MAX_EST][NSLOT]; };
+using NceWs = NceWsT<64>;
+using NceWsWide = NceWsT<128>;
 static_assert(sizeof(NceWs) <= NCE_WS_FLOATS * sizeof(float), "NCE_WS_FLOATS (estimator_ops.h) too small");
+static_assert(sizeof(NceWsWide) <= NCE_WS_WIDE_FLOATS * sizeof(float), "NCE_WS_WIDE_FLOATS (estimator_ops.h) too small");
+template <int NV, class WS>
 __global__ __launch_bounds__(1024) void mi_infonce_rows_kernel(const float* __restrict__ scores, float* __restrict__ dscores, float* __restrict__ mi,
-                                                               float* __restrict__ mil, const float* __restrict__ gscale, int B, NceWs* __restrict__ ws) {
+                                                               float* __restrict__ mil, const float* __restrict__ gscale, int B, WS* __restrict__ ws) {
   __shared__ float red[16];
   __shared__ int last;
   const int e = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -253,21 +272,21 @@ __global__ __launch_bounds__(1024) void mi_infonce_rows_kernel(const float* __re
   float part = 0.f;
   if (i < B) {                                                     // (wave-uniform)
     const float* __restrict__ row = scores + ((long)e * B + i) * B;
-    float v[16], mx = -INFINITY;
+    float v[NV], mx = -INFINITY;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) { const int j = lane + 64 * q; v[q] = j < B ? row[j] : -INFINITY; mx = fmaxf(mx, v[q]); }
+    for (int q = 0; q < NV; ++q) { const int j = lane + 64 * q; v[q] = j < B ? row[j] : -INFINITY; mx = fmaxf(mx, v[q]); }
     const float sii = row[i];
     mx = wave_max(mx);
     float se = 0.f;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) se += __expf(v[q] - mx);           // (padding: e^{-inf} = 0)
+    for (int q = 0; q < NV; ++q) se += __expf(v[q] - mx);           // (padding: e^{-inf} = 0)
     se = wave_sum(se);
     const float lse = mx + __logf(se);
     if (lane == 0) part = sii - lse;
     if (dscores) {
       float* __restrict__ drow = dscores + ((long)e * B + i) * B;
 #pragma unroll
-      for (int q = 0; q < 16; ++q) {
+      for (int q = 0; q < NV; ++q) {
         const int j = lane + 64 * q;
         if (j < B) drow[j] = gs * invB * ((i == j ? 1.f : 0.f) - __expf(v[q] - lse));
       }
@@ -872,14 +891,24 @@ int mi_sep_nce_tiled(hipStream_t s, const float* tout, float* dtout, float* mi, 
 
 int mi_bound_fwd_bwd(hipStream_t s, const float* scores, float* dscores, float* mi, float* mil, const float* gscale, int E,
                      int B, int bound, unsigned lossform, const float* lb, float* dlb, long lb_stride, float* nce_ws) {
-  if (B > 1024) return set_error(MIMRL_ERR_ARG, "mi_bound: batch %d > 1024 per rank", B);
+  if (B < 1 || B > MIMRL_MAX_BATCH) return set_error(MIMRL_ERR_ARG, "mi_bound: batch %d outside [1, MIMRL_MAX_BATCH = %d]", B, MIMRL_MAX_BATCH);
+  const bool wide = B > 1024;
   if (bound == BOUND_INFONCE && E <= NCE_MAX_EST && nce_ws) {   // row-wise bound: one wave per row (the general kernel -- no shared state -- is one workgroup per estimator)
-    hipLaunchKernelGGL(mi_infonce_rows_kernel, dim3((B + 15) / 16, E), dim3(1024), 0, s, scores, dscores, mi, mil, gscale, B, reinterpret_cast<NceWs*>(nce_ws));
+    if (wide)
+      hipLaunchKernelGGL((mi_infonce_rows_kernel<32, NceWsWide>), dim3((B + 15) / 16, E), dim3(1024), 0, s, scores, dscores, mi, mil, gscale, B,
+                         reinterpret_cast<NceWsWide*>(nce_ws));
+    else
+      hipLaunchKernelGGL((mi_infonce_rows_kernel<16, NceWs>), dim3((B + 15) / 16, E), dim3(1024), 0, s, scores, dscores, mi, mil, gscale, B,
+                         reinterpret_cast<NceWs*>(nce_ws));
     LAUNCH_CHECK();
     return MIMRL_OK;
   }
-  hipLaunchKernelGGL(mi_bound_kernel, dim3(E), dim3(1024), 0, s, scores, dscores, mi, mil, gscale, B, bound, lossform, lb, dlb,
-                     lb_stride);
+  if (wide)
+    hipLaunchKernelGGL(mi_bound_wide_kernel, dim3(E), dim3(1024), (size_t)6 * B * sizeof(float), s, scores, dscores, mi, mil, gscale, B, bound,
+                       lossform, lb, dlb, lb_stride);
+  else
+    hipLaunchKernelGGL(mi_bound_kernel, dim3(E), dim3(1024), 0, s, scores, dscores, mi, mil, gscale, B, bound, lossform, lb, dlb,
+                       lb_stride);
   LAUNCH_CHECK();
   return MIMRL_OK;
 }

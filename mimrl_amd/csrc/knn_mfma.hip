@@ -665,7 +665,15 @@ int sample_anchors(hipStream_t s, const AnchorDraws& d, int m, int N, uint32_t s
   const uint32_t thr0 = frac >= 1.0 ? 0xffffffffu : (uint32_t)(frac * 4294967296.0);
   const int cap = (int)std::min<long>((long)N, 4L * m + 256);
   const size_t sh = (size_t)cap * sizeof(unsigned long long);
-  if (sh > 60 * 1024) return set_error(MIMRL_ERR_ARG, "sample_anchors: %d anchors per call exceed the LDS candidate list", m);
+  // above 60 KiB (more than 1856 anchors per call: k = 1 with B > 1856) the candidate list takes up to 150 KiB of dynamic LDS
+  if (sh > 150 * 1024) return set_error(MIMRL_ERR_ARG, "sample_anchors: %d anchors per call exceed the LDS candidate list", m);
+  if (sh > 60 * 1024) {
+    static bool attr = false;
+    if (!attr) {
+      HIPX(hipFuncSetAttribute(reinterpret_cast<const void*>(sample_anchors_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+      attr = true;
+    }
+  }
   hipLaunchKernelGGL(sample_anchors_kernel, dim3(d.n), dim3(1024), sh, s, d, m, N, cap, thr0, seed_lo, seed_hi, step);
   LAUNCH_CHECK();
   return MIMRL_OK;
