@@ -251,6 +251,20 @@ int mimrl_op_gru_forward(void* stream, const float* gx_f, const float* gx_r, con
 int mimrl_op_gru_backward(void* stream, const float* whh_f, const float* whh_r, const float* saved_f,
                           const float* saved_r, const int32_t* lens, const float* out, const float* dout, float* dg_f,
                           float* dg_r, float* hprev_f, float* hprev_r, int B, int T, int precision);
+/* (ABI v6) batch rows per workgroup of the GRU and LSTM recurrence launches (1..4) for B rows of nmod modalities: the last workgroup's
+ * padding lanes mirror its last real row when B % btv != 0.  An error if the two encoders' picks ever differ. */
+int mimrl_op_recur_btv(int B, int nmod);
+/* (ABI v6) one bidirectional LSTM layer (Model.py:250-252, packed sequences), one modality: gx_* [B,T,512] = x W_ih^T + b_ih per direction
+ * (gate order i,f,g,o), out [B,T,256] (forward | reverse), saved_* [B,T,768] (null, both: no record) -- kernel: 0 the scalar fp32 kernels,
+ * 1 the fp32 MFMA kernels, 2 the bf16-operand MFMA kernels, exactly that one (the engine picks through MIMRL_LSTM_* instead) */
+int mimrl_op_lstm_forward(void* stream, const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r,
+                          const float* bhh_f, const float* bhh_r, const int32_t* lens, float* out, float* saved_f,
+                          float* saved_r, int B, int T, int kernel);
+/* BPTT of that layer: dout [B,T,256], each direction reads its own half; dg_* [B,T,512] the gradient w.r.t. the gate pre-activations
+ * (= d gx = d(h W_hh^T)), hprev_* [B,T,128] h_{t-1} of every step (0 at sequence starts and padded steps) */
+int mimrl_op_lstm_backward(void* stream, const float* whh_f, const float* whh_r, const float* saved_f,
+                           const float* saved_r, const int32_t* lens, const float* out, const float* dout, float* dg_f,
+                           float* dg_r, float* hprev_f, float* hprev_r, int B, int T, int kernel);
 /* (ABI v6) the layer-0 weight gradients of four (modality, direction) sequences in ONE pass over dg (gru_wgrad.hip; autograd of nn.GRU,
  * Model.py:254-255): dw_ih[s] [384, kp] += dgx_s^T x_s, dw_hh[s] [384, 128] += dgh_s^T hp_s with dg[s] [rows, 512], x[s] [rows, kp], hp[s]
  * [rows, 128] all STORED as bf16 (dgx / dgh as in mimrl_op_gru_backward); kp a multiple of 8, <= 96; x[s] of the two directions of a

@@ -116,6 +116,9 @@ def load() -> C.CDLL:
                                   C.c_float, C.c_float]
     lib.mimrl_op_gru_forward.argtypes = [_FP] * 11 + [C.c_int, C.c_int, C.c_int]
     lib.mimrl_op_gru_backward.argtypes = [_FP] * 12 + [C.c_int, C.c_int, C.c_int]
+    lib.mimrl_op_lstm_forward.argtypes = [_FP] * 11 + [C.c_int, C.c_int, C.c_int]
+    lib.mimrl_op_lstm_backward.argtypes = [_FP] * 12 + [C.c_int, C.c_int, C.c_int]
+    lib.mimrl_op_recur_btv.argtypes = [C.c_int, C.c_int]
     lib.mimrl_op_concat_dw.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 7 + [C.c_int]
     lib.mimrl_op_gru_wgrad.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5 + [C.c_int64, C.c_int]
     lib.mimrl_op_mi_bound.argtypes = [_FP] * 5 + [C.c_int, C.c_int, C.c_int]
@@ -170,7 +173,7 @@ EXPORTS = [
     "mimrl_op_cmi_loss", "mimrl_op_sample_anchors", "mimrl_knn_r1_host", "mimrl_set_knn_override_mask", "mimrl_op_mlp_stack_forward", "mimrl_op_mlp_stack_backward", "mimrl_op_adam",
     "mimrl_probe_cube", "mimrl_probe_mi", "mimrl_probe_cmi", "mimrl_probe_knn", "mimrl_probe_encoders", "mimrl_set_kernel_stamps", "mimrl_comm_unique_id", "mimrl_set_comm", "mimrl_main_late_offset", "mimrl_set_comm_critic_bf16",
     "mimrl_stage1_pipe_prime", "mimrl_stage1_pipe", "mimrl_set_task_loss", "mimrl_op_task_loss",
-    "mimrl_op_mi_infonce_rows",
+    "mimrl_op_mi_infonce_rows", "mimrl_op_lstm_forward", "mimrl_op_lstm_backward", "mimrl_op_recur_btv",
 ]
 
 # --loss (Parameters.py:55, Solver.py:172-192) -> MIMRL_TASK_LOSS_*

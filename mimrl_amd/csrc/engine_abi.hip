@@ -616,6 +616,41 @@ int mimrl_op_gru_backward(void* stream, const float* whh_f, const float* whh_r, 
   return gru_backward(reinterpret_cast<hipStream_t>(stream), a, (precision & 1) != 0);
 }
 
+int mimrl_op_recur_btv(int B, int nmod) {
+  if (B < 1 || nmod < 1 || nmod > 2) return set_error(MIMRL_ERR_ARG, "mimrl_op_recur_btv: B >= 1, nmod 1 or 2");
+  const int g = gru_pick_btv(B, nmod), l = lstm_btv(B, nmod);
+  if (g != l) return set_error(MIMRL_ERR_STATE, "mimrl_op_recur_btv: the GRU (%d) and LSTM (%d) picks differ: give this entry point an encoder argument", g, l);
+  return g;
+}
+
+int mimrl_op_lstm_forward(void* stream, const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r,
+                          const float* bhh_f, const float* bhh_r, const int32_t* lens, float* out, float* saved_f,
+                          float* saved_r, int B, int T, int kernel) {
+  if (!gx_f || !gx_r || !whh_f || !whh_r || !bhh_f || !bhh_r || !lens || !out) return set_error(MIMRL_ERR_ARG, "mimrl_op_lstm_forward: null argument");
+  if ((saved_f != nullptr) != (saved_r != nullptr)) return set_error(MIMRL_ERR_ARG, "mimrl_op_lstm_forward: both saved records or neither");
+  LstmFwdArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.B = B; a.T = T; a.out_ld = 2 * H; a.nmod = 1;
+  a.lens[0] = lens; a.lens[1] = lens;
+  a.seq[0][0] = LstmSeq{gx_f, whh_f, bhh_f, out, saved_f};
+  a.seq[0][1] = LstmSeq{gx_r, whh_r, bhh_r, out, saved_r};
+  return lstm_forward_kernels(reinterpret_cast<hipStream_t>(stream), a, kernel);
+}
+
+int mimrl_op_lstm_backward(void* stream, const float* whh_f, const float* whh_r, const float* saved_f,
+                           const float* saved_r, const int32_t* lens, const float* out, const float* dout, float* dg_f,
+                           float* dg_r, float* hprev_f, float* hprev_r, int B, int T, int kernel) {
+  if (!whh_f || !whh_r || !saved_f || !saved_r || !lens || !out || !dout || !dg_f || !dg_r || !hprev_f || !hprev_r)
+    return set_error(MIMRL_ERR_ARG, "mimrl_op_lstm_backward: null argument");
+  LstmBwdArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.B = B; a.T = T; a.out_ld = 2 * H; a.dout_ld = 2 * H; a.nmod = 1;
+  a.lens[0] = lens; a.lens[1] = lens;
+  a.seq[0][0] = LstmSeqBwd{whh_f, saved_f, out, dout, dg_f, hprev_f};
+  a.seq[0][1] = LstmSeqBwd{whh_r, saved_r, out, dout + H, dg_r, hprev_r};     // each direction reads its own half of dout
+  return lstm_backward_kernels(reinterpret_cast<hipStream_t>(stream), a, kernel);
+}
+
 int mimrl_op_concat_dw(void* stream, const void* dz2, const void* a1, float* dw2, const void* dz1, const void* a0, float* dw1, int E, int64_t rows,
                        int64_t dw_stride, const float* ds, const void* a2h, float* dw3, const uint32_t* m2, const float* w3, const float* P,
                        const float* Q, int B) {

@@ -1,7 +1,8 @@
 // 1-layer bidirectional LSTM encoder of `--encoders lstm` (Model.py:250-252,441-447), packed-sequence semantics.
 // Round 5: on the matrix cores like the bi-GRU (persistent workgroups of 4 batch rows, W_hh as register-resident MFMA B fragments, fp32
 // MFMA = exact parity mode, bf16 operands in the bf16 mode); the round-1 scalar design -- one workgroup per (sample, direction,
-// modality), 512 threads = the 512 gate rows -- stays as the reference the operator test compares with (MIMRL_LSTM_SCALAR=1).
+// modality), 512 threads = the 512 gate rows -- stays reachable (MIMRL_LSTM_SCALAR=1).  Every kernel is reachable by name through
+// mimrl_op_lstm_forward / _backward, which tests/test_gpu_recurrence_tiling.py compares with float64 autograd of the oracle.
 #pragma once
 #include "common.h"
 
@@ -21,8 +22,10 @@ struct LstmFwdArgs {
   const int* lens[2];
   int B, T, out_ld, nmod;
 };
-// mode: 0 scalar fp32 reference kernels, 1 fp32 MFMA (exact), 2 bf16 MFMA operands -- see lstm.hip
+// mode: 1 fp32 precision, 2 bf16 operands; the MIMRL_LSTM_* knobs pick the kernels (lstm.hip: lstm_mode) -- the engine's entry point
 int lstm_forward(hipStream_t s, const LstmFwdArgs& a, int mode = 1);
+// kernel: 0 scalar fp32 kernels, 1 fp32 MFMA (exact), 2 bf16 MFMA operands -- runs exactly that kernel, no knob (the operator entry points)
+int lstm_forward_kernels(hipStream_t s, const LstmFwdArgs& a, int kernel);
 
 struct LstmSeqBwd {
   const float* w_hh;   // [4H,H]
@@ -38,5 +41,8 @@ struct LstmBwdArgs {
   int B, T, out_ld, dout_ld, nmod;
 };
 int lstm_backward(hipStream_t s, const LstmBwdArgs& a, int mode = 1);
+int lstm_backward_kernels(hipStream_t s, const LstmBwdArgs& a, int kernel);
+// batch rows per workgroup of the MFMA kernels (1..4; the last tile's padding lanes mirror its last real row)
+int lstm_btv(int B, int nmod);
 
 }  // namespace mimrl

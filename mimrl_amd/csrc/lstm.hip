@@ -121,7 +121,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(LstmBwdArgs a) {
 //   BPTT:     the dg tile [4, 4H] goes through LDS, carry = dg . W_hh: 32 products per step over k = 512
 // Padding lanes mirror the last real row (no guarded access in the loop), positions t >= length emit 0 and do not advance the state.
 // The saved record and the dg / h_prev outputs keep lstm.h's fp32 layouts (the weight-gradient GEMMs of the engine are unchanged).
-// The scalar kernels above stay as the reference implementation the operator-level test compares this one with.
+// The scalar kernels above stay as the round-1 fp32 implementation (MIMRL_LSTM_SCALAR=1, and the fp32 mode's default).
 // =====================================================================================================================================
 constexpr int G4M = 4 * LSTM_H;
 #include "recur_device.h"
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_mfma_kernel(LstmBwdArgs a, in
 
 }  // namespace
 
-static int lstm_btv(int B, int nmod) {
+int lstm_btv(int B, int nmod) {
   int btv = (B * nmod * 2 + 127) / 128;      // ~128 workgroups, at most 4 rows each (the recurrence is latency-bound: spread it out)
   return btv < 1 ? 1 : (btv > BR ? BR : btv);
 }
@@ -319,9 +319,12 @@ static int lstm_mode(int mode) {
   return mode;
 }
 
-int lstm_forward(hipStream_t s, const LstmFwdArgs& a, int mode) {
+int lstm_forward(hipStream_t s, const LstmFwdArgs& a, int mode) { return lstm_forward_kernels(s, a, lstm_mode(mode)); }
+int lstm_backward(hipStream_t s, const LstmBwdArgs& a, int mode) { return lstm_backward_kernels(s, a, lstm_mode(mode)); }
+
+int lstm_forward_kernels(hipStream_t s, const LstmFwdArgs& a, int mode) {
   if (a.B <= 0 || a.T <= 0) return set_error(MIMRL_ERR_ARG, "lstm_forward: empty batch");
-  mode = lstm_mode(mode);
+  if (mode < 0 || mode > 2) return set_error(MIMRL_ERR_ARG, "lstm_forward: kernel %d is not 0 (scalar), 1 (fp32 MFMA) or 2 (bf16 MFMA)", mode);
   const bool save = a.seq[0][0].saved != nullptr;
   if (mode == 0) {
     hipLaunchKernelGGL(lstm_fwd_kernel, dim3(a.B, 2, a.nmod), dim3(512), 0, s, a);
@@ -340,9 +343,9 @@ int lstm_forward(hipStream_t s, const LstmFwdArgs& a, int mode) {
   return MIMRL_OK;
 }
 
-int lstm_backward(hipStream_t s, const LstmBwdArgs& a, int mode) {
+int lstm_backward_kernels(hipStream_t s, const LstmBwdArgs& a, int mode) {
   if (a.B <= 0 || a.T <= 0) return set_error(MIMRL_ERR_ARG, "lstm_backward: empty batch");
-  mode = lstm_mode(mode);
+  if (mode < 0 || mode > 2) return set_error(MIMRL_ERR_ARG, "lstm_backward: kernel %d is not 0 (scalar), 1 (fp32 MFMA) or 2 (bf16 MFMA)", mode);
   if (mode == 0) {
     hipLaunchKernelGGL(lstm_bwd_kernel, dim3(a.B, 2, a.nmod), dim3(512), 0, s, a);
   } else {

@@ -21,8 +21,9 @@ CONFIGS = {
                            baseline="gaussain"),
     # --encoders lstm (1-layer bi-LSTM, Model.py:250-252), ragged inputs
     "tiny_lstm": dict(B=8, T=6, N=40, seed=9, critic="separate", cube="6-3-128=4-3-128", traj=2, ragged=True, encoders="lstm"),
-    # --encoders lstm at BASELINE cfg1's shape (B = 32, T = 50, ragged lengths: four rows of different lengths per recurrence workgroup):
-    # the MFMA LSTM kernels of round 5 (lstm.hip) against the reference's nn.LSTM on packed sequences
+    # --encoders lstm at BASELINE cfg1's shape (B = 32, T = 50, ragged lengths): the MFMA LSTM kernels of round 5 (lstm.hip) against the
+    # reference's nn.LSTM on packed sequences.  B = 32 with two modalities gives ONE batch row per recurrence workgroup (mimrl_op_recur_btv);
+    # tests/test_gpu_recurrence_tiling.py covers 2-4 rows per workgroup and partial last tiles
     "cfg1_lstm": dict(B=32, T=50, N=1000, seed=17, critic="separate", cube="50-3-128=10-3-128", traj=2, ragged=True, encoders="lstm"),
     # interpolated bound (VMI.py:201-250) with the constant baseline, concat critic
     "tiny_interp": dict(B=8, T=6, N=40, seed=8, critic="concat", cube="6-3-128=4-3-128", traj=2, bound="interpolate"),
@@ -32,8 +33,8 @@ CONFIGS = {
     # BASELINE cfg1: B=32, T=50, canonical README flags, N=1000 as in the reference smoke test (Model.py:607)
     "cfg1_sep": dict(B=32, T=50, N=1000, seed=0, critic="separate", cube="50-3-128=10-3-128", traj=6),
     "cfg1_cat": dict(B=32, T=50, N=1000, seed=0, critic="concat", cube="50-3-128=10-3-128", traj=1),
-    # N1 at benchmark scale: cfg1 / cfg2 with RAGGED a/v lengths -- packed-sequence GRU semantics (Model.py:425-447) with
-    # four batch rows of different lengths per recurrence workgroup at T = 50
+    # N1 at benchmark scale: cfg1 / cfg2 with RAGGED a/v lengths -- packed-sequence GRU semantics (Model.py:425-447) at T = 50;
+    # cfg1 (B = 32) runs one batch row per recurrence workgroup, cfg2 (B = 128) four rows of different lengths per workgroup in full tiles
     "cfg1_ragged": dict(B=32, T=50, N=1000, seed=15, critic="separate", cube="50-3-128=10-3-128", traj=2, ragged=True),
     "cfg2_ragged": dict(B=128, T=50, N=1284, seed=16, critic="separate", cube="50-3-128=10-3-128", traj=1, ragged=True),
     # BASELINE cfg2 at FULL size (the bench configuration: B=128, T=50, MOSI-sized banks)

@@ -209,7 +209,7 @@ def mi_terms_q(p, opt, feats, rnd):
 
 
 # --------------------------------------------------------------------------------------
-# encoders: W_t projection + 2-layer bi-GRU (gemm_fast_f16 + gru.hip) with the kernels' rounding points
+# encoders: W_t projection + 2-layer bi-GRU (gemm_fast_f16 + gru.hip) or 1-layer bi-LSTM (lstm.hip) with the kernels' rounding points
 # --------------------------------------------------------------------------------------
 class _GruDirQ(torch.autograd.Function):
     """One direction of one nn.GRU layer on the hoisted input projection gx = x W_ih^T + b_ih, forward AND backward written out as
@@ -224,9 +224,11 @@ class _GruDirQ(torch.autograd.Function):
                              the layer below, both products of `mm`) round it themselves, the same value the bf16-stored dg holds.
     With rq = identity this IS autograd of oracle.gru_direction (tests/test_rounded_ref.py)."""
     @staticmethod
-    def forward(ctx, gx, w_hh, b_hh, lengths, reverse, rq, qd=identity, qh=identity):
+    def forward(ctx, gx, w_hh, b_hh, lengths, reverse, rq, qd=identity, qh=identity, tape=None):
         """qd / qh (round 5b, MIMRL_REC16): storage rounding of the BPTT's two streamed operands -- dout as its producer stored it (bf16: the dh0
-        product's epilogue / the LayerNorm backward) and h_prev as the forward kernel's fp16 copy of its outputs (layer 0)."""
+        product's epilogue / the LayerNorm backward) and h_prev as the forward kernel's fp16 copy of its outputs (layer 0).
+        tape (a dict, optional): the backward leaves the BPTT kernel's two outputs in it -- tape["dg"] [B,T,4H] = [dr'|dz'|dn'|dn'*r] and
+        tape["hp"] [B,T,H] -- for the operator-level tests, which compare them element by element."""
         B, T, G = gx.shape
         H = G // 3
         wq = rq(w_hh)
@@ -246,16 +248,17 @@ class _GruDirQ(torch.autograd.Function):
             h = torch.where(valid, hnew, h)
             gates[:, t] = torch.stack([r, z, n, hn], 1)
         ctx.save_for_backward(rq(gates), out, wq, lengths)
-        ctx.meta = (order, rq, qd, qh)
+        ctx.meta = (order, rq, qd, qh, tape)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         gates, out, wq, lengths = ctx.saved_tensors
-        order, rq, qd, qh = ctx.meta
+        order, rq, qd, qh, tape = ctx.meta
         B, T, H = out.shape
         carry = out.new_zeros(B, H)
         dgx = out.new_zeros(B, T, 3 * H)
+        dg_all, hp_all = out.new_zeros(B, T, 4 * H), out.new_zeros(B, T, H)
         dw = torch.zeros_like(wq)
         db = out.new_zeros(3 * H)
         for k in range(len(order) - 1, -1, -1):
@@ -280,10 +283,13 @@ class _GruDirQ(torch.autograd.Function):
             dhz = torch.where(valid, dh * z, carry)
             dgh = torch.cat([drp, dzp, dnr], 1)
             dgx[:, t] = torch.cat([drp, dzp, dnp], 1)
+            dg_all[:, t], hp_all[:, t] = torch.cat([drp, dzp, dnp, dnr], 1), hp
             carry = dhz + rq(dgh) @ wq
             dw = dw + rq(dgh).t() @ rq(hp)
             db = db + dgh.sum(0)
-        return dgx, dw, db, None, None, None, None, None
+        if tape is not None:
+            tape["dg"], tape["hp"] = dg_all, hp_all
+        return dgx, dw, db, None, None, None, None, None, None
 
 
 def bigru2_q(p, prefix, x, lengths, rnd, rq, gxq=identity, rec16=False):
@@ -303,13 +309,91 @@ def bigru2_q(p, prefix, x, lengths, rnd, rq, gxq=identity, rec16=False):
     return inp[..., :H] + inp[..., H:]
 
 
-def encoders_q(p, opt, t_feat, a, v, rnd, rq, gxq=identity, rec16=False):
+class _LstmDirQ(torch.autograd.Function):
+    """One direction of nn.LSTM(d, H, 1) on the hoisted input projection gx = x W_ih^T + b_ih, forward AND backward written out as lstm.hip
+    computes them (Model.py:250-252,441-447 packed semantics: positions t >= length emit 0 and advance neither h nor c), with ``rq`` at the
+    kernels' rounding points:
+      lstm_fwd_mfma_kernel<bf16>  per cell step the fp32 state h and W_hh are rounded for the product h W_hh^T, which accumulates in fp32 on
+                                  top of gx + b_hh; the gates, the cell state c and the saved record (i, f, g, o, c_prev, tanh c) stay fp32.
+      lstm_bwd_mfma_kernel<bf16>  dh = dout + carry, dc and the gate gradients dg = [di'|df'|dg'|do'] in fp32 from the fp32 record; the carry
+                                  product dg W_hh with both operands rounded; dg and h_prev leave as fp32.  The engine's weight-gradient
+                                  GEMMs (bf16 mode) round their operands: dW_hh = sum_t rq(dg_t)^T rq(h_prev_t); db_hh = sum_t dg_t is a
+                                  fp32 column sum; the gradient w.r.t. gx is dg itself.
+    With rq = identity this IS autograd of oracle.lstm_direction (tests/test_rounded_ref.py).  tape: as _GruDirQ's (dg [B,T,4H], hp)."""
+    @staticmethod
+    def forward(ctx, gx, w_hh, b_hh, lengths, reverse, rq, tape=None):
+        B, T, G = gx.shape
+        H = G // 4
+        wq = rq(w_hh)
+        h, c = gx.new_zeros(B, H), gx.new_zeros(B, H)
+        out = gx.new_zeros(B, T, H)
+        rec = gx.new_zeros(B, T, 6, H)
+        order = list(range(T - 1, -1, -1)) if reverse else list(range(T))
+        for t in order:
+            g = gx[:, t] + b_hh + rq(h) @ wq.t()
+            i, f, gg, o = torch.sigmoid(g[:, :H]), torch.sigmoid(g[:, H:2 * H]), torch.tanh(g[:, 2 * H:3 * H]), torch.sigmoid(g[:, 3 * H:])
+            cn = f * c + i * gg
+            tc = torch.tanh(cn)
+            hn = o * tc
+            valid = (lengths > t).unsqueeze(1)
+            rec[:, t] = torch.stack([i, f, gg, o, c, tc], 1)
+            out[:, t] = torch.where(valid, hn, torch.zeros_like(hn))
+            h = torch.where(valid, hn, h)
+            c = torch.where(valid, cn, c)
+        ctx.save_for_backward(rec, out, wq, lengths)
+        ctx.meta = (order, rq, tape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        rec, out, wq, lengths = ctx.saved_tensors
+        order, rq, tape = ctx.meta
+        B, T, H = out.shape
+        dh_c, dc_c = out.new_zeros(B, H), out.new_zeros(B, H)
+        dg_all, hp_all = out.new_zeros(B, T, 4 * H), out.new_zeros(B, T, H)
+        dw = torch.zeros_like(wq)
+        for k in range(len(order) - 1, -1, -1):
+            t = order[k]
+            valid = (lengths > t).unsqueeze(1)
+            if k > 0:
+                tp = order[k - 1]
+                hp = torch.where(valid & (lengths > tp).unsqueeze(1), out[:, tp], torch.zeros_like(dh_c))
+            else:
+                hp = torch.zeros_like(dh_c)
+            i, f, gg, o, cp, tc = (rec[:, t, j] for j in range(6))
+            dh = dout[:, t] + dh_c
+            dc = dc_c + dh * o * (1 - tc * tc)
+            dg = torch.cat([dc * gg * i * (1 - i), dc * cp * f * (1 - f), dc * i * (1 - gg * gg), dh * tc * o * (1 - o)], 1)
+            dg = torch.where(valid, dg, torch.zeros_like(dg))
+            dc_c = torch.where(valid, dc * f, dc_c)
+            dh_c = torch.where(valid, rq(dg) @ wq, dh_c)
+            dg_all[:, t], hp_all[:, t] = dg, hp
+            dw = dw + rq(dg).t() @ rq(hp)
+        if tape is not None:
+            tape["dg"], tape["hp"] = dg_all, hp_all
+        return dg_all, dw, dg_all.sum((0, 1)), None, None, None, None
+
+
+def bilstm1_q(p, prefix, x, lengths, rnd, rq):
+    """oracle.bilstm1 with the kernels' rounding: the hoisted projections through ``mm`` (``rnd``), the recurrences through _LstmDirQ (``rq``)."""
+    outs = [_LstmDirQ.apply(mm(x, p[f"{prefix}.weight_ih_l0{sfx}"], rnd) + p[f"{prefix}.bias_ih_l0{sfx}"], p[f"{prefix}.weight_hh_l0{sfx}"],
+                            p[f"{prefix}.bias_hh_l0{sfx}"], lengths, rev, rq)
+            for rev, sfx in ((False, ""), (True, "_reverse"))]
+    return outs[0] + outs[1]
+
+
+def encoders_q(p, opt, t_feat, a, v, rnd, rq, gxq=identity, rec16=False, lstm_rnd=None):
     """Model.forward up to the stacked cube input (Model.py:395-475; oracle.model_forward lines 187-206), dropout 0.
-    -> (x [B,L,3,D], T_F, A_F, V_F)."""
+    -> (x [B,L,3,D], T_F, A_F, V_F).  opt.encoders "lstm": bilstm1_q, whose input projections round as ``lstm_rnd`` says (the engine runs them
+    as plain GEMMs: bf16 operands in both passes in the bf16 mode, BF16; None: ``rnd``); gxq / rec16 are the GRU path's."""
     D, L = opt.d_common, opt.time_len
     t = mm(t_feat, p["W_t.weight"], rnd)
     la, lv = R.infer_lengths(a), R.infer_lengths(v)
-    ah = F.relu(F.layer_norm(bigru2_q(p, "rnn_a", a, la, rnd, rq, gxq, rec16), (D,), p["ln_a.weight"], p["ln_a.bias"], 1e-6))
-    vh = F.relu(F.layer_norm(bigru2_q(p, "rnn_v", v, lv, rnd, rq, gxq, rec16), (D,), p["ln_v.weight"], p["ln_v.bias"], 1e-6))
+    if getattr(opt, "encoders", "gru") == "lstm":
+        enc = lambda pre, x, ln_: bilstm1_q(p, pre, x, ln_, rnd if lstm_rnd is None else lstm_rnd, rq)
+    else:
+        enc = lambda pre, x, ln_: bigru2_q(p, pre, x, ln_, rnd, rq, gxq, rec16)
+    ah = F.relu(F.layer_norm(enc("rnn_a", a, la), (D,), p["ln_a.weight"], p["ln_a.bias"], 1e-6))
+    vh = F.relu(F.layer_norm(enc("rnn_v", v, lv), (D,), p["ln_v.weight"], p["ln_v.bias"], 1e-6))
     pad = lambda y: F.pad(y, (0, 0, 0, L - y.shape[1]))
     return torch.stack([pad(t), pad(ah), pad(vh)], dim=2), t.mean(1), ah.mean(1), vh.mean(1)

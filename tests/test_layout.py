@@ -23,6 +23,17 @@ def test_library_exports_every_declared_symbol():
     assert lib.mimrl_abi_version() == 6
 
 
+def test_recurrence_rows_per_workgroup():
+    """mimrl_op_recur_btv (host only): ceil(2 B nmod / 128) rows per recurrence workgroup, 1..4 -- the pick the GRU and LSTM launches make,
+    through which tests/test_gpu_recurrence_tiling.py asserts the tiling each of its cases is named for; bad arguments are refused."""
+    lib = _lib.load()
+    for B, nmod, want in ((8, 2, 1), (32, 2, 1), (33, 2, 2), (64, 1, 1), (65, 1, 2), (67, 1, 2), (131, 1, 3), (199, 1, 4), (37, 2, 2),
+                          (70, 2, 3), (99, 2, 4), (128, 2, 4), (1025, 2, 4), (2048, 2, 4)):
+        assert lib.mimrl_op_recur_btv(B, nmod) == want, (B, nmod)
+    for B, nmod in ((0, 1), (4, 0), (4, 3)):
+        assert lib.mimrl_op_recur_btv(B, nmod) < 0
+
+
 @pytest.mark.parametrize("name", list(CONFIGS))
 def test_native_layout_matches_python(name):
     opt = make_opt(CONFIGS[name])

@@ -113,3 +113,73 @@ def test_identity_rounding_is_the_oracles_gru_and_its_autograd():
     for a, b in ((tf, T_F), (af, A_F), (vf, V_F)):
         assert (a - b).abs().max() < 1e-12
     assert (R.cube_mlp(p, opt, xq).mean(2).mean(1) - F_F).abs().max() < 1e-12
+
+
+def test_identity_rounding_is_the_oracles_lstm_and_its_autograd():
+    """_LstmDirQ writes lstm.hip's forward AND BPTT out by hand (to place the bf16 kernels' rounding points); with the identity hook it must be
+    oracle.lstm_direction and torch autograd of it -- ragged lengths (1, T, values between, a row that ends before the reverse direction
+    starts elsewhere), both directions, a different upstream gradient per direction -- its tape must hold the BPTT outputs the
+    operator test compares with (dg = d gx, h_prev), and the lstm branch of encoders_q must be the first half of oracle.model_forward."""
+    torch.manual_seed(1)
+    B, T, D, H = 6, 7, 5, 128
+    x = torch.randn(B, T, D, dtype=torch.float64, requires_grad=True)
+    lens = torch.tensor([7, 1, 4, 7, 2, 6])
+    ws = [(torch.randn(4 * H, D, dtype=torch.float64) * 0.3).requires_grad_(True), (torch.randn(4 * H, H, dtype=torch.float64) * 0.1).requires_grad_(True),
+          (torch.randn(4 * H, dtype=torch.float64) * 0.1).requires_grad_(True), (torch.randn(4 * H, dtype=torch.float64) * 0.1).requires_grad_(True)]
+    for rev in (False, True):
+        do = torch.randn(B, T, H, dtype=torch.float64)
+        o1 = R.lstm_direction(x, lens, ws[0], ws[1], ws[2], ws[3], rev)
+        g1 = torch.autograd.grad((o1 * do).sum(), [x] + ws)
+        gx = (Q.mm(x, ws[0], Q.EXACT) + ws[2]).detach().requires_grad_(True)
+        tape = {}
+        o2 = Q._LstmDirQ.apply(gx, ws[1], ws[3], lens, rev, Q.identity, tape)
+        assert (o1 - o2).abs().max() < 1e-12
+        g2 = torch.autograd.grad((o2 * do).sum(), [gx, ws[1], ws[3]])
+        assert (tape["dg"] - g2[0]).abs().max() == 0
+        dgx = g2[0].reshape(B * T, 4 * H)
+        for a, b in ((g1[0], (dgx @ ws[0]).reshape(B, T, D)), (g1[1], dgx.t() @ x.reshape(B * T, D)), (g1[2], g2[1]), (g1[3], dgx.sum(0)),
+                     (g1[4], g2[2]), (g1[2], tape["dg"].reshape(B * T, 4 * H).t() @ tape["hp"].reshape(B * T, H))):
+            assert (a - b).abs().max() < 1e-12
+        # h_prev: the previous step's output in visiting order, 0 at the sequence start and at padded steps
+        for b_ in range(B):
+            for t in range(T):
+                tp = t + 1 if rev else t - 1
+                want = o1[b_, tp] if 0 <= tp < T and t < lens[b_] and tp < lens[b_] else torch.zeros(H, dtype=torch.float64)
+                assert (tape["hp"][b_, t] - want.detach()).abs().max() < 1e-12
+    c, opt, batch, banks = case("tiny_lstm", torch.float64)
+    p = oracle_params(opt, c["seed"], torch.float64)
+    assert opt.encoders == "lstm"
+    xq, tf, af, vf = Q.encoders_q(p, opt, batch[0], batch[1], batch[2], Q.EXACT, Q.identity, lstm_rnd=Q.EXACT)
+    pred, F_F, T_F, A_F, V_F = R.model_forward(p, opt, batch[0], batch[1], batch[2])
+    for a, b in ((tf, T_F), (af, A_F), (vf, V_F)):
+        assert (a - b).abs().max() < 1e-12
+    assert (R.cube_mlp(p, opt, xq).mean(2).mean(1) - F_F).abs().max() < 1e-12
+    # and its gradients: every rnn_a / rnn_v tensor, through the custom backward of mm and _LstmDirQ, against autograd of bilstm1
+    la = R.infer_lengths(batch[1])
+    names = [n for n in p if n.startswith("rnn_a.")]
+    assert len(names) == 8
+    res = []
+    for fn in (lambda q: R.bilstm1(q, "rnn_a", batch[1], la), lambda q: Q.bilstm1_q(q, "rnn_a", batch[1], la, Q.EXACT, Q.identity)):
+        leaves = {n: p[n].clone().requires_grad_(True) for n in names}
+        out = fn({**p, **leaves})
+        res.append(torch.autograd.grad((out * torch.sin(torch.arange(out.numel(), dtype=torch.float64)).reshape(out.shape)).sum(),
+                                       [leaves[n] for n in names]))
+    for n, a, b in zip(names, *res):
+        assert (a - b).abs().max() < 1e-12, n
+
+
+def test_rounded_lstm_is_not_the_exact_one():
+    """the bf16 hook really reaches the LSTM recurrence (both passes): a rounded reference equal to the exact one would let a kernel that
+    skips its rounding pass the tight band"""
+    torch.manual_seed(2)
+    B, T, H = 3, 5, 128
+    gx = torch.randn(B, T, 4 * H, dtype=torch.float64, requires_grad=True)
+    w, b = torch.randn(4 * H, H, dtype=torch.float64) * 0.1, torch.randn(4 * H, dtype=torch.float64) * 0.1
+    lens = torch.tensor([5, 3, 1])
+    do = torch.randn(B, T, H, dtype=torch.float64)
+    res = []
+    for rq in (Q.identity, Q.r_bf16):
+        o = Q._LstmDirQ.apply(gx, w, b, lens, True, rq)
+        res.append((o, torch.autograd.grad((o * do).sum(), gx)[0]))
+    assert 1e-6 < (res[0][0] - res[1][0]).abs().max() < 1e-2
+    assert 1e-6 < (res[0][1] - res[1][1]).abs().max() / res[0][1].abs().max() < 3e-2
