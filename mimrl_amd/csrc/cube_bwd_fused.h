@@ -31,7 +31,7 @@ struct DAxisBwdArgs {
   int act;                                     // id == hd == od == 128
   // optional (all four or none): parameter gradients that are column sums over the rows of what this kernel holds anyway --
   // dgamma = sum dz * xhat, dbeta = sum dz (LayerNorm), db2 = sum dY, db1 = sum dU; accumulated with atomics ([128] each).
-  // Null: the caller runs rowln_param_grads / colsum side kernels instead.
+  // Null: the caller runs daxis_param_grads as a side kernel instead.
   float *dgamma, *dbeta, *db2, *db1;
 };
 bool daxis_bwd_supported(int id, int hd, int od);
@@ -45,10 +45,6 @@ int wt_transpose_bf16(hipStream_t s, const WtTransposeArgs& a);
 // db2 = sum dY, db1 = sum dU (db2 / db1 may be null); accumulated with atomics
 int daxis_param_grads(hipStream_t s, const float* y, const float* mean, const float* rstd, const float* dz, const float* dy,
                       const float* du, float* dgamma, float* dbeta, float* db2, float* db1, long R);
-
-// LayerNorm(D) parameter gradients as column sums over rows: dgamma[j] = sum_r dz * xhat, dbeta[j] = sum_r dz
-int rowln_param_grads(hipStream_t s, const float* y, const float* mean, const float* rstd, const float* dz, float* dgamma,
-                      float* dbeta, long R, int n);
 
 #ifdef MIMRL_PHASE_PROBE
 int cube_bwd_read_phases(long long* out);   // 64 ticks, see cube_bwd_fused.hip

@@ -458,26 +458,10 @@ __global__ void wt_transpose_kernel(WtTransposeArgs a) {
   for (int j = ty; j < 32; j += 8) dst[(n0 + j) * 128 + k0 + tx] = to_bf16(t[tx][j]);
 }
 
-__global__ void rowln_param_grads_kernel(const float* __restrict__ y, const float* __restrict__ mean,
-                                         const float* __restrict__ rstd, const float* __restrict__ dz,
-                                         float* __restrict__ dgamma, float* __restrict__ dbeta, long R, int n) {
-  // thread = column j (n <= 256), rows strided over the grid
-  const int j = threadIdx.x;
-  if (j >= n) return;
-  float sg = 0.f, sb = 0.f;
-  for (long r = blockIdx.x; r < R; r += gridDim.x) {
-    const float g = dz[r * n + j];
-    sg += g * (y[r * n + j] - mean[r]) * rstd[r];
-    sb += g;
-  }
-  acc_add(&dgamma[j], sg);
-  acc_add(&dbeta[j], sb);
-}
-
 // All four column-sum parameter gradients of the D axis in one streaming pass over dz, y, dY, dU ([R,128] each):
 //   dgamma = sum dz * xhat, dbeta = sum dz, db2 = sum dY, db1 = sum dU.
 // Workgroup = 64 rows: thread = (column quad, row lane), 8 rows each with 16-byte loads; LDS reduction over the 8 row lanes,
-// then 512 atomics.  (Replaces rowln_param_grads + 2 x colsum: 3 launches of 30-40 us each at R = 19,200.)
+// then 512 atomics.  (Replaced a LayerNorm parameter-gradient kernel + 2 x colsum: 3 launches of 30-40 us each at R = 19,200.)
 __global__ __launch_bounds__(256) void daxis_param_grads_kernel(const float* __restrict__ y, const float* __restrict__ mean,
                                                                 const float* __restrict__ rstd, const float* __restrict__ dz,
                                                                 const float* __restrict__ dy, const float* __restrict__ du,
@@ -542,15 +526,6 @@ int daxis_bwd_fused(hipStream_t s, const DAxisBwdArgs& a) {
 int wt_transpose_bf16(hipStream_t s, const WtTransposeArgs& a) {
   if (a.n < 1 || a.n > 12) return set_error(MIMRL_ERR_ARG, "wt_transpose_bf16: 1..12 matrices");
   hipLaunchKernelGGL(wt_transpose_kernel, dim3(4, 4, a.n), dim3(256), 0, s, a);
-  LAUNCH_CHECK();
-  return MIMRL_OK;
-}
-
-int rowln_param_grads(hipStream_t s, const float* y, const float* mean, const float* rstd, const float* dz, float* dgamma,
-                      float* dbeta, long R, int n) {
-  if (n > 256) return set_error(MIMRL_ERR_ARG, "rowln_param_grads: row length %d > 256", n);
-  const int grid = (int)(R < 512 ? R : 512);
-  hipLaunchKernelGGL(rowln_param_grads_kernel, dim3(grid), dim3(256), 0, s, y, mean, rstd, dz, dgamma, dbeta, R, n);
   LAUNCH_CHECK();
   return MIMRL_OK;
 }

@@ -96,7 +96,7 @@ bool det_launch_accumulates(const char* name) {
     // kernels whose every acc_add target is a gradient-bucket tensor (checked against the sources, round 5b): LayerNorm / bias / weight
     // gradients of the model backward and the estimator stacks, the BPTT's bias gradients, column / row sums into the buckets
     static const char* const kBucketOnly[] = {"ln_relu_drop_bwd", "head_bwd_kernel", "colln_bwd_kernel", "rowln_bwd_kernel", "kmix_bwd_kernel",
-                                              "colsum_kernel", "rowsum_batched", "colln_param_grads", "daxis_param_grads", "rowln_param_grads",
+                                              "colsum_kernel", "rowsum_batched", "colln_param_grads", "daxis_param_grads",
                                               "laxis_bwd_kernel", "daxis_bwd_kernel", "gru_bwd_kernel", "top1_bwd_kernel", "concat_dw3_kernel",
                                               "mlp_frag_kernel", "gemm_group_kernel", "gemm_groupk_kernel"};
     for (const char* k : kBucketOnly)

@@ -20,7 +20,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
-#include <functional>
 #include <vector>
 #include <dlfcn.h>
 
@@ -143,7 +142,7 @@ struct mimrl_handle {
   bool boundary_in_adam = false;       // the stage boundary rode on the critic Adam launch (enqueue_apply -> run)
   bool img_valid = false;
   unsigned knn_ovr_mask[2] = {0u, 0u};  // per stage: CMI calls whose neighbour rows come from bufs.knn_override
-  bool knn_pre = true;                 // prefetch mode: stage 2's kNN sampling also runs inside stage 1, beside the encoder prefix (MIMRL_NO_KNN_PREFETCH=1: off)
+  bool knn_pre = true;                 // prefetch mode: stage 2's kNN sampling also runs inside stage 1, beside the encoder prefix
   bool mi_fused_bwd_done = false;      // mi_forward already produced the tower-output gradients (mi_sep_fused)
   bool imgT_ready = false;             // a transposed-image refresh has been issued for the estimator pass being enqueued
   TransposeTable ttab;
@@ -259,8 +258,6 @@ struct mimrl_handle {
   float *tin = nullptr, *ta[3], *tout = nullptr, *scores = nullptr, *dscores = nullptr;
   float *cP = nullptr, *cQ = nullptr, *ca[3];
   int split_part = 0;                  // 1: encoders_backward stops behind the layer-1 weight gradients (mimrl_stage_grads_part); 0: whole pass
-  std::function<int()> pending_text;   // MIMRL_TEXT_LATE: the text branch captured behind the layer-0 input projection (1) / recurrence (2)
-  int pending_text_at = 0;
   bool fold_unpack = false, unpack_pending = false;   // the packed layer-0 GRU weight gradients are scattered by the Adam launch (AdamArgs::fold)
   bool fold_unpack_on = true;          // MIMRL_NO_FOLD_UNPACK=1: keep the separate scatter kernel (tuning knob)
   bool gx_f16 = false;                 // the hoisted GRU input projections gx[B,T,3H] are stored as fp16 (long sequences, bf16 mode: create)
@@ -468,7 +465,7 @@ struct mimrl_handle {
 
   int G_(const GemmDesc& d) { return G_on(stream, d); }
   // (rounds 2-5 had an accuracy-bisection knob here -- MIMRL_FWD_FP32_SITES: single forward sites with fp32 operands in bf16 mode; the rounded-
-  //  operand oracle tests of round 4 replaced that use, the knob went in round 6)
+  //  operand oracle tests of round 4 replaced that use, the knob was removed in round 6)
   static constexpr bool fp32_site(int) { return false; }
   struct PrecGuard {   // run a scope with fp32 GEMM operands
     mimrl_handle* h; bool saved;
@@ -481,8 +478,8 @@ struct mimrl_handle {
                     const float *p1 = nullptr, *p2 = nullptr, *p3 = nullptr; float* dst2 = nullptr; KMixW kw = KMixW();
                     const float *p4 = nullptr, *p5 = nullptr; float *dst3 = nullptr, *dst4 = nullptr; };
   std::vector<Deferred> deferred;
-  int flush_deferred(int only_side = 0, hipEvent_t after = nullptr);
-  int wg_helper = -1;                  // side stream that takes every second weight-gradient GEMM of an MLP stack (-1: none)
+  int flush_deferred(int only_side = 0);
+  int wg_helper = -1;                  // side stream for weight-gradient GEMMs of an MLP stack beside the data-gradient chain / the grouped launch (-1: none)
   int dbg_delay(hipStream_t st, int tag);   // critical-path probe (MIMRL_DBG_DELAY_TAG / _US): a spin kernel behind one phase
   int model_forward(bool train, bool save, int knn_stage = 0, int part = 0);   // part: 0 all, 1 prefix, 2 tail
   int cube_forward(bool train, bool save);
@@ -510,7 +507,6 @@ struct mimrl_handle {
   GatherSum head_gather;               // sources of the F_F gradient (summed inside head_bwd) while head_gather_on
   bool head_gather_on = false;
   hipEvent_t ev_dmean = nullptr;       // T / A / V feature gradients ready (gathered on side 0)
-  hipEvent_t ev_pre = nullptr;         // MIMRL_BPTT_FIRST: the point the parked kernels are flushed behind (encoders_backward -> gru_layer_backward)
   int estimators_all(int stage, bool want_grad, bool backward);
   // grouped MLP stacks living in the critic bucket (nb groups, uniform parameter stride `pstride`)
   int mlp_stack_forward(int nb, int rows, int brows, long p0, long pstride, int nl, const long (*l_off)[2], const int* dims,

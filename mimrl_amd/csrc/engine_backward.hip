@@ -8,9 +8,8 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
   for (int i = 0; i < cfg.n_blocks; ++i)
     for (int ax = 0; ax < 3; ++ax) dims[i + 1][ax] = cfg.d_outs[i][ax];
   // deferred mode: every gradient buffer is used once (weight-gradient GEMMs read dY / dU after the chain has moved on)
-  constexpr bool no_defer = false;   // (an environment knob until round 5: fixed at its measured optimum)
   const int per_block = 7 + (cfg.dropout_mlp[0] > 0.f) + (cfg.dropout_mlp[2] > 0.f);   // buffers one block consumes
-  const bool defer = multi_stream && !cfg.ln_first && !no_defer && per_block * cfg.n_blocks + 1 <= NGBUF;
+  const bool defer = multi_stream && !cfg.ln_first && per_block * cfg.n_blocks + 1 <= NGBUF;
   const int npool = defer ? NGBUF : 4;
   int used[NGBUF] = {0};
   used[cur_in] = 1;
@@ -38,16 +37,6 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
       return MIMRL_OK;
     }
     return colln_param_grads(S(sd), y, mean, rstd, dz, dgam, dbet, nb, n, cols);
-  };
-  auto W_lnrow = [&](int sd, const float* y, const float* mean, const float* rstd, const float* dz, float* dgam, float* dbet,
-                     long rows, int n) -> int {
-    if (defer) {
-      Deferred d{4, sd, GemmDesc(), y, rows, n, 0, 0, dgam};
-      d.p1 = mean; d.p2 = rstd; d.p3 = dz; d.dst2 = dbet;
-      deferred.push_back(d);
-      return MIMRL_OK;
-    }
-    return rowln_param_grads(S(sd), y, mean, rstd, dz, dgam, dbet, rows, n);
   };
   auto W_dpg = [&](int sd, const float* y, const float* mean, const float* rstd, const float* dz, const float* dy, const float* du,
                    float* dgam, float* dbet, float* db2, float* db1, long rows) -> int {
@@ -87,25 +76,16 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
       fa.w2t = wtT[i][0]; fa.w1t = wtT[i][1]; fa.wrt = wtT[i][2];
       fa.dy = gbuf[i_dy]; fa.du = gbuf[i_du]; fa.dx = gbuf[i_dx];
       fa.R = R2; fa.act = cfg.activation;
-      // LayerNorm and bias gradients (column sums over the rows of dz, y, dY, dU).  Folded into the data-gradient kernel they cost
-      // the chain 13 us per block (MIMRL_DAXIS_PG_FUSE=1: 19 -> 32 us); as ONE streaming side kernel instead of rowln_param_grads +
-      // 2 x colsum (3 launches of 30-40 us each) they are ~10 us beside the BPTT (MIMRL_NO_DAXIS_PG_ONE=1: the three launches)
-      constexpr bool pg_fuse = false;        // (an environment knob until round 5: fixed at its measured optimum)
-      constexpr bool no_pg_one = false;
-      const bool pg_fused = pg_fuse && a.fc2.b >= 0 && a.fc1.b >= 0;
-      const bool pg_one = !pg_fused && !no_pg_one;
+      // LayerNorm and bias gradients (column sums over the rows of dz, y, dY, dU): ONE streaming side kernel, ~10 us beside the BPTT
+      // (folded into the data-gradient kernel, or as three separate launches: DESIGN.md section 7)
       fa.dgamma = fa.dbeta = fa.db2 = fa.db1 = nullptr;
-      if (pg_fused) { fa.dgamma = Gm(a.ln_g); fa.dbeta = Gm(a.ln_b); fa.db2 = Gm(a.fc2.b); fa.db1 = Gm(a.fc1.b); }
       MX(daxis_bwd_fused(stream, fa));
       MX(W_fork(1, 3));
-      if (pg_one) MX(W_dpg(2, b.d.y, b.d.mean, b.d.rstd, gbuf[cur], gbuf[i_dy], gbuf[i_du], Gm(a.ln_g), Gm(a.ln_b),
-                           a.fc2.b >= 0 ? Gm(a.fc2.b) : nullptr, a.fc1.b >= 0 ? Gm(a.fc1.b) : nullptr, R2));
-      if (!pg_fused && !pg_one) MX(W_lnrow(2, b.d.y, b.d.mean, b.d.rstd, gbuf[cur], Gm(a.ln_g), Gm(a.ln_b), R2, od));
+      MX(W_dpg(2, b.d.y, b.d.mean, b.d.rstd, gbuf[cur], gbuf[i_dy], gbuf[i_du], Gm(a.ln_g), Gm(a.ln_b),
+               a.fc2.b >= 0 ? Gm(a.fc2.b) : nullptr, a.fc1.b >= 0 ? Gm(a.fc1.b) : nullptr, R2));
       { GemmDesc g = gemm_tn(gbuf[i_dy], od, b.d.h, hd, Gm(a.fc2.w), hd, od, hd, (int)R2); g.atomic = 1; MX(W_gemm(1, g)); }
-      if (!pg_fused && !pg_one && a.fc2.b >= 0) MX(W_colsum(1, gbuf[i_dy], R2, od, od, Gm(a.fc2.b)));
       { GemmDesc g = gemm_tn(gbuf[i_dy], od, b.k.z, id, Gm(a.res), id, od, id, (int)R2); g.atomic = 1; MX(W_gemm(2, g)); }
       { GemmDesc g = gemm_tn(gbuf[i_du], hd, b.k.z, id, Gm(a.fc1.w), id, hd, id, (int)R2); g.atomic = 1; MX(W_gemm(3, g)); }
-      if (!pg_fused && !pg_one && a.fc1.b >= 0) MX(W_colsum(3, gbuf[i_du], R2, hd, hd, Gm(a.fc1.b)));
       MX(W_join(1, 3));
       release(cur); release(i_dy); release(i_du);
       cur = i_dx;
@@ -353,23 +333,17 @@ int mimrl_handle::dbg_delay(hipStream_t st, int tag) {
   return MIMRL_OK;
 }
 
-// `after`: an event recorded earlier on the main stream; the side streams then wait for THAT point instead of the main
-// stream's current position (lets the caller enqueue -- and, in a captured graph, order -- main-stream work in front of the
-// parked kernels without making them depend on it)
-int mimrl_handle::flush_deferred(int only_side, hipEvent_t after) {
+int mimrl_handle::flush_deferred(int only_side) {
   if (deferred.empty()) return MIMRL_OK;
-  if (after && multi_stream) {
-    for (int i = 1; i <= 3; ++i) if (side_on(i)) HIPX(hipStreamWaitEvent(side[i], after, 0));
-  } else if (only_side > 0) MX(fork(only_side, only_side)); else MX(fork(1, 3));
+  if (only_side > 0) MX(fork(only_side, only_side)); else MX(fork(1, 3));
   for (int q = 1; q <= 3; ++q) MX(dbg_delay(S(q), 9));
   constexpr int wg_sides = 3;
   static const int dbg_skip_kinds = dbg_env("MIMRL_DBG_SKIP_DEFERRED") ? atoi(dbg_env("MIMRL_DBG_SKIP_DEFERRED")) : 0;   // timing experiments only (bit = kind)
   // the weight-gradient GEMMs as (at most) two grouped split-K launches, one per operand-layout class: D-axis products are
   // (RC,RC), the batch-reduced L-axis products (KC,KC).  Alone each is a ~20 us launch of 4..64 tiles.
-  constexpr bool no_wg_groupk = false;   // (an environment knob until round 5: fixed at its measured optimum)
   // (short sequences only: at T = 1000 the recurrence beside them runs for a millisecond, launch latencies are hidden and one
   // chip-filling launch in front of the BPTT costs more than it saves -- cfg5: 3.85 vs 3.74 ms)
-  const bool groupk = !no_wg_groupk && !prof_on && bf16 && !((dbg_skip_kinds >> 0) & 1) && cfg.seq_len <= 128;
+  const bool groupk = !prof_on && bf16 && !((dbg_skip_kinds >> 0) & 1) && cfg.seq_len <= 128;
   if (groupk) {
     std::vector<GemmDesc> cls[2];
     for (const Deferred& d : deferred) if (d.kind == 0) cls[d.g.sa_k == 1 ? 0 : 1].push_back(d.g);
@@ -388,7 +362,6 @@ int mimrl_handle::flush_deferred(int only_side, hipEvent_t after) {
     else if (d.kind == 1) MX(colsum(st, d.src, d.n0, (int)d.n1, (int)d.n2, d.dst));
     else if (d.kind == 2) MX(rowsum_batched(st, d.src, (int)d.n0, (int)d.n1, (int)d.n2, d.dst));
     else if (d.kind == 3) MX(colln_param_grads(st, d.src, d.p1, d.p2, d.p3, d.dst, d.dst2, (int)d.n0, (int)d.n1, (int)d.n2));
-    else if (d.kind == 4) MX(rowln_param_grads(st, d.src, d.p1, d.p2, d.p3, d.dst, d.dst2, d.n0, (int)d.n1));
     else if (d.kind == 6) MX(daxis_param_grads(st, d.src, d.p1, d.p2, d.p3, d.p4, d.p5, d.dst, d.dst2, d.dst3, d.dst4, d.n0));
     else MX(kmix_bwd_part(st, d.src, d.p3, nullptr, d.kw, d.n0, (int)d.n1, 2));
   }
@@ -428,15 +401,7 @@ int mimrl_handle::encoders_backward(float* dcube) {
   // capture order of the two consumers (graph nodes are dispatched in capture order): the LayerNorm backward, head of the critical
   // BPTT chain, first; the text branch (35 us of W_t weight gradient with slack until the end of the stage) behind it.  History: while
   // the side streams were congested by the parked CubeMLP weight gradients the opposite order was faster (1.229 vs 1.259 ms); with the
-  // grouped / fused parameter-gradient kernels it is this one (0.980 vs 0.988 ms).  MIMRL_TEXT_BWD_FIRST=1: the other order.
-  constexpr bool text_bwd_first = false;
-  auto text_bwd = [&]() -> int {   // text branch (side 0): dW_t = dtx^T . text
-    MX(fork(0, 0));
-    MX(text_post_bwd(S(0), dcube, dtx, B, T, L, 3, D, 0, cfg.dropout[0], key(), 0, dmean));
-    { GemmDesc g = gemm_tn(dtx, D, bufs.text, cfg.d_t, Gm(w_t), cfg.d_t, D, cfg.d_t, (int)BT_); g.atomic = 1; MX(G_on(S(0), g)); }
-    return MIMRL_OK;
-  };
-  if (text_bwd_first) MX(text_bwd());
+  // grouped / fused parameter-gradient kernels it is this one (0.980 vs 0.988 ms).
   if (head_gather_on && ev_dmean) { HIPX(hipStreamWaitEvent(stream, ev_dmean, 0)); ev_dmean = nullptr; }   // dmean gathered on side 0
   // audio / video: LN+ReLU+dropout backward -> ds (shared by both directions of layer 1)
   {
@@ -448,23 +413,18 @@ int mimrl_handle::encoders_backward(float* dcube) {
     ds_bf16_live = rec16_on && cfg.encoder == MIMRL_ENCODER_GRU && dg_bf16 && (prec & MIMRL_PREC_BF16_GRU_BWD) != 0 && gru_bwd_io16_ok(0);
     MX(ln_relu_drop_bwd2(stream, sd[0], sd[1], dcube, B, T, L, 3, D, key(), dmean + (size_t)B * D, dmean + 2 * (size_t)B * D, ds_bf16_live ? 1 : 0));
   }
-  if (!text_bwd_first) MX(text_bwd());
-  // CubeMLP weight gradients: side 1..3, beside the layer-1 BPTT.  Tuning knob MIMRL_BPTT_FIRST=1 captures the BPTT launch in
-  // front of the parked kernels (graph nodes are dispatched in capture order).  Measured on cfg2: 1.58 vs 1.36 ms -- the
-  // recurrence is latency-bound and loses more to the weight-gradient kernels sharing its CUs from the first cell step on
-  // than the ~100 us it waits behind their first wave; default off.
+  // text branch (side 0): dW_t = dtx^T . text
+  MX(fork(0, 0));
+  MX(text_post_bwd(S(0), dcube, dtx, B, T, L, 3, D, 0, cfg.dropout[0], key(), 0, dmean));
+  { GemmDesc g = gemm_tn(dtx, D, bufs.text, cfg.d_t, Gm(w_t), cfg.d_t, D, cfg.d_t, (int)BT_); g.atomic = 1; MX(G_on(S(0), g)); }
+  // CubeMLP weight gradients: side 1..3, beside the layer-1 BPTT and captured IN FRONT of it (graph nodes are dispatched in capture
+  // order).  The BPTT launch first measured 1.58 vs 1.36 ms on cfg2 -- the recurrence is latency-bound and loses more to the
+  // weight-gradient kernels sharing its CUs from the first cell step on than the ~100 us it waits behind their first wave.
   // debugging: make the main stream wait for sides 1..3 (the parked kernels) at point n: 1 before the BPTT, 2 behind the layer-1 BPTT,
   // 3 behind the dh0 product, 4 behind the layer-0 BPTT
   static const int dbg_join_at = dbg_env("MIMRL_DBG_JOIN_AT") ? atoi(dbg_env("MIMRL_DBG_JOIN_AT")) : 0;
-  constexpr bool bptt_first = false;
-  ev_pre = nullptr;
-  if (bptt_first && multi_stream && cfg.encoder == MIMRL_ENCODER_GRU && !deferred.empty()) {
-    MX(next_event(&ev_pre));
-    HIPX(hipEventRecord(ev_pre, stream));
-  } else {
-    MX(flush_deferred());
-    if (dbg_join_at == 1) MX(join(1, 3));
-  }
+  MX(flush_deferred());
+  if (dbg_join_at == 1) MX(join(1, 3));
   if (cfg.encoder != MIMRL_ENCODER_GRU) kmix_pg_on_side3 = false;   // (joined with every other side at the end of those paths)
   if (cfg.encoder == MIMRL_ENCODER_CONV) {
     MX(conv_backward());
@@ -516,16 +476,12 @@ int mimrl_handle::gru_layer_backward(int l) {
     }
     { Scope sc(this, MIMRL_PH_GRU_BWD); MX(gru_backward(stream, a, (prec & MIMRL_PREC_BF16_GRU_BWD) != 0)); }
     if ((l == 1 && dbg_join_at == 2) || (l == 0 && dbg_join_at == 4)) MX(join(1, 3));
-    if (l == 1 && ev_pre) MX(flush_deferred(0, ev_pre));
     MX(dbg_delay(stream, 8));
-    // side streams of the GRU weight gradients (tuning knobs).  Sides 1..3 still carry the parked CubeMLP parameter-gradient
-    // kernels at this point; sides 0 (text branch), 4 and 5 (kNN sampler, CMI branch) have been idle since the forward pass.
-    constexpr int l0_side = 1;
-    constexpr int l1_side0 = 1;
-    MX(fork(1, (l == 0 || l1_side0 == 4) ? 5 : 3));   // the weight gradients below depend on the BPTT only
-    if (l0_side == 0 && l == 0) MX(fork(0, 0));
-    constexpr bool dh0_last = false;   // (an environment knob until round 5: fixed at its measured optimum): capture order of dh0 vs the side-stream weight gradients
-    auto dh0_gemm = [&]() -> int {   // gradient to the layer-0 outputs, dh0 = sum_dir dgx_dir . W_ih_l1_dir
+    // side streams of the GRU weight gradients.  Sides 1..3 still carry the parked CubeMLP parameter-gradient kernels at this point;
+    // sides 0 (text branch), 4 and 5 (kNN sampler, CMI branch) have been idle since the forward pass -- and stay so.
+    constexpr int l0_side = 1;   // side stream of the packed layer-0 dW_hh product
+    MX(fork(1, l == 0 ? 5 : 3));   // the weight gradients below depend on the BPTT only
+    if (l == 1) {   // gradient to the layer-0 outputs, dh0 = sum_dir dgx_dir . W_ih_l1_dir: captured in front of the side-stream weight gradients
       dh0_bf16_live = false;
       // one dual-product GEMM (both directions accumulate in the same output tile), batch = modality
       {
@@ -555,9 +511,7 @@ int mimrl_handle::gru_layer_backward(int l) {
         }
         MX(G_(q));
       }
-      return MIMRL_OK;
-    };
-    if (l == 1 && !dh0_last) MX(dh0_gemm());
+    }
     if (l == 1 && dbg_join_at == 3) MX(join(1, 3));
     // weight gradients of this layer: off the critical path.  Layer 1: side 1..3 (they overlap the layer-0 BPTT);
     // layer 0 is the tail of the stage.
@@ -617,9 +571,8 @@ int mimrl_handle::gru_layer_backward(int l) {
       auto two = [&](GemmDesc& q, long a_o, long b_o, long c_o) { if (both) { q.batch = 4; q.batch_in = 2; q.sa_bo = a_o; q.sb_bo = b_o; q.sc_bo = c_o; } };
       const long o_dg = dg[l][1][0] - dg[l][0][0], o_hp = hprev[l][1][0] - hprev[l][0][0], o_in = both ? h0[1] - h0[0] : 0;
       const long o_wih = gru[1][l][0].w_ih - gru[0][l][0].w_ih, o_whh = gru[1][l][0].w_hh - gru[0][l][0].w_hh;
-      constexpr int tail_n = 1;   // (an environment knob until round 5: fixed at its measured optimum)
       constexpr int wg_sides = 3;
-      auto pick = [&]() { if (l == 0) { const int q = rr++ % tail_n; return q == 0 ? stream : S(q); } return l1_side0 == 4 ? S(4 + rr++ % 2) : S(1 + rr++ % wg_sides); };
+      auto pick = [&]() { return l == 0 ? stream : S(1 + rr++ % wg_sides); };   // layer 0 is the tail of the stage: main stream only
       { GemmDesc q = gemm_tn(dg[l][m][0], 4 * H, in, gf.din, Gm(gf.w_ih), gf.din, G, gf.din, (int)BT_);
         q.batch = 2; q.sa_b = s_dg; q.sb_b = 0; q.sc_b = gr.w_ih - gf.w_ih; q.atomic = 1; two(q, o_dg, o_in, o_wih);
         if (lbf) { q.a_bf16 = 1; q.sa_b *= 2; q.sa_bo *= 2; }
@@ -636,7 +589,6 @@ int mimrl_handle::gru_layer_backward(int l) {
         if (lbf) { q.a_bf16 = q.b_bf16 = 1; q.sa_b *= 2; q.sa_bo *= 2; q.sb_b *= 2; q.sb_bo *= 2; }
         MX(G_on(pick(), q)); }
     }
-    if (l == 1 && dh0_last) MX(dh0_gemm());
   }
   return MIMRL_OK;
 }

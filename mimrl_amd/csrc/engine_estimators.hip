@@ -47,8 +47,7 @@ int mimrl_handle::mlp_stack_backward(int nb, int rows, int brows, long p0, long 
   const bool use_fused = bf16 && fused_mlp && fused_bwd && imgT_ready && rows <= 512 && nl <= 4 && mlp_fused_supported(nb, rows, nl, dims);
   // single-output top layer (the concat critic's score head) over many rows: one streaming kernel instead of three GEMMs with
   // one real column in 64 (dz, dW, both bias gradients)
-  constexpr bool no_top1 = false;   // (an environment knob until round 5: fixed at its measured optimum)
-  const bool top1 = !use_fused && !no_top1 && dims[nl] == 1 && nl >= 2 && dims[nl - 1] % 4 == 0 && dims[nl - 1] <= 1024 && 1024 % dims[nl - 1] == 0 &&
+  const bool top1 = !use_fused && dims[nl] == 1 && nl >= 2 && dims[nl - 1] % 4 == 0 && dims[nl - 1] <= 1024 && 1024 % dims[nl - 1] == 0 &&
                     dtmp[0] != nullptr;
   if (wgrad && !use_fused && !top1)   // bias gradient of the top layer; the lower ones come out of the dA GEMM epilogues below
     MX(colsum(stream, dout, rows, dims[nl], dims[nl], CG(p0 + l_off[nl - 1][1]), nb, (long)brows * dims[nl], pstride));
@@ -68,15 +67,12 @@ int mimrl_handle::mlp_stack_backward(int nb, int rows, int brows, long p0, long 
     if (wgrad) fa.db_top = CG(p0 + l_off[nl - 1][1]);   // the top layer's bias gradient rides along (was a separate column-sum launch)
     // ... and so does the weight gradient of a narrow top layer (the 2-logit CMI head: not eligible for the grouped launch, it was a
     // 17 us generic GEMM in front of it on the CMI branch of stage 1)
-    constexpr bool no_top_wg = false;   // (an environment knob until round 5: fixed at its measured optimum)
-    const bool top_wg = wgrad && !no_top_wg && dims[nl] % 4 != 0 && mlp_bwd_takes_top_wgrad(fa);
+    const bool top_wg = wgrad && dims[nl] % 4 != 0 && mlp_bwd_takes_top_wgrad(fa);
     if (top_wg) fa.dw_top = CG(p0 + l_off[nl - 1][0]);
     MX(mlp_stack_bwd_fused(stream, fa));
     if (!wgrad) return MIMRL_OK;
-    // the nl weight-gradient GEMMs are independent of each other: on the critical branch (wg_helper >= 0) every second
-    // one goes to a helper side stream
-    constexpr bool no_split = false;   // (an environment knob until round 5: fixed at its measured optimum)
-    const int hs = (multi_stream && !no_split) ? wg_helper : -1;
+    // on the critical branch (wg_helper >= 0) a product the grouped launch below cannot take goes to a helper side stream
+    const int hs = multi_stream ? wg_helper : -1;
     if (hs >= 0) MX(fork(hs, hs));
     GemmDesc gs[MLPF_MAX_LAYERS];
     for (int l = nl - 1; l >= 0; --l) {   // dW_l = dZ_l^T A_l
@@ -90,21 +86,14 @@ int mimrl_handle::mlp_stack_backward(int nb, int rows, int brows, long p0, long 
     }
     // the nl weight-gradient products are independent of each other: ONE grouped launch (gemm_group; it falls back to nl launches
     // when a product is not eligible, e.g. the 2-row top layer of the CMI classifiers, which then goes alone)
-    constexpr bool no_group = false;   // (an environment knob until round 5: fixed at its measured optimum): the round-1 schedule (helper stream, alternating)
-    if (!no_group) {
-      int lo = 0;
-      if (top_wg) lo = 1;                                                             // done inside the data-gradient kernel
-      else if (dims[nl] % 4 != 0) { MX(G_on(hs >= 0 ? S(hs) : stream, gs[0])); lo = 1; }   // not row-contiguous-eligible: beside the group
-      MX(G_group(stream, gs + lo, nl - lo));
-    } else {
-      constexpr int helper_par = 0;   // (an environment knob until round 5: fixed at its measured optimum)
-      for (int q = top_wg ? 1 : 0; q < nl; ++q) MX(G_on((hs >= 0 && (q & 1) == helper_par) ? S(hs) : stream, gs[q]));
-    }
+    int lo = 0;
+    if (top_wg) lo = 1;                                                             // done inside the data-gradient kernel
+    else if (dims[nl] % 4 != 0) { MX(G_on(hs >= 0 ? S(hs) : stream, gs[0])); lo = 1; }   // not row-contiguous-eligible: beside the group
+    MX(G_group(stream, gs + lo, nl - lo));
     if (hs >= 0) MX(join(hs, hs));
     return MIMRL_OK;
   }
-  constexpr bool no_big_side = false;   // (an environment knob until round 5: fixed at its measured optimum)
-  const bool big_side = wgrad && multi_stream && !no_big_side && wg_helper >= 0 && rows >= 2048 && nl <= 3;
+  const bool big_side = wgrad && multi_stream && wg_helper >= 0 && rows >= 2048 && nl <= 3;
   for (int l = nl - 1; l >= 0; --l) {
     const int din_ = dims[l], dout_ = dims[l + 1];
     const float* a_in = l == 0 ? in : act[l - 1];
@@ -502,8 +491,7 @@ int mimrl_handle::route_feature_grads() {
   }
   // The F slot's sum is folded into head_bwd (its only consumer); T / A / V are needed only behind the CubeMLP backward: side 0,
   // off the chain (was one launch + a queue hop between the stage-2 estimators and the head: ~20 us)
-  constexpr bool no_head_gather = false;   // (an environment knob until round 5: fixed at its measured optimum)
-  head_gather_on = !no_head_gather && multi_stream && side_on(0);
+  head_gather_on = multi_stream && side_on(0);
   if (!head_gather_on) return gather_sum4(stream, g4, B, EMB);
   head_gather = g4.g[0];
   MX(fork(0, 0));
@@ -519,7 +507,6 @@ int mimrl_handle::estimators_all(int stage, bool want_grad, bool backward) {
   DetDefer det_defer(stream, &det_ranges);   // (deterministic build, det.h: the stacks' weight / bias gradients are flushed once, at the end of the stage's estimator work)
   const bool bf_fwd = (prec & MIMRL_PREC_BF16_GEMM_FWD) != 0 && !fp32_site(8), bf_bwd = (prec & MIMRL_PREC_BF16_GEMM_BWD) != 0;
   static const bool dbg_skip_imgt = dbg_env("MIMRL_DBG_SKIP_IMGT") != nullptr;   // timing experiments only (stale images: wrong gradients)
-  constexpr bool imgt_first = false;         // (an environment knob until round 5: fixed at its measured optimum)
   bool imgT_pending = false;
   imgT_ready = false;
   if (frag_side_pending) { MX(join(3, 3)); frag_side_pending = false; }
@@ -534,8 +521,8 @@ int mimrl_handle::estimators_all(int stage, bool want_grad, bool backward) {
     if (!(skip_imgT_refresh && stage == 1)) {                         // built beside the forward stacks (combined step: once per step,
       MX(fork(3, 3));                                                 // in stage 2 -- stage 1 of the NEXT step sees the same critics)
       // capture order: the launch itself goes BEHIND the CMI branch's forward kernels (see cmi_branch) -- graph nodes are dispatched in
-      // capture order, and as the first child of the stage boundary it held up both forward branches by ~18 us (MIMRL_IMGT_FIRST=1)
-      imgT_pending = !imgt_first && multi_stream && side_on(3) && side_on(5);
+      // capture order, and as the first child of the stage boundary it held up both forward branches by ~18 us
+      imgT_pending = multi_stream && side_on(3) && side_on(5);
       if (!imgT_pending) MX(frag_tr_launch(S(3)));
       if (!imgT_pending && !dbg_skip_imgt) MX(bf16_transposed_images(S(3), bufs.crit_p, crit_imgT, ttab));
     }
@@ -545,37 +532,28 @@ int mimrl_handle::estimators_all(int stage, bool want_grad, bool backward) {
   static const int dbg_skip = dbg_env("MIMRL_DBG_SKIP_EST") ? atoi(dbg_env("MIMRL_DBG_SKIP_EST")) : 0;   // timing experiments only
   MX(fork(5, 5));
   MX(chain(5, 4));                       // the CMI branch needs the kNN indices
-  constexpr int interleave = 0;
-  const bool imgT_late = ((interleave >> (stage - 1)) & 1) && interleave >= 4;   // 4 + mask: the image launches on side 3 are captured behind BOTH forward halves
-  auto imgT_launch = [&]() -> int {   // side 3 already waits for the stage boundary (fork above); only the launch was held back
-    imgT_pending = false;
-    MX(frag_tr_launch(side[3]));
-    if (!dbg_skip_imgt) MX(bf16_transposed_images(side[3], bufs.crit_p, crit_imgT, ttab));
-    return MIMRL_OK;
-  };
-  // part: 1 = forward, 2 = backward, 3 = both
-  auto cmi_branch = [&](int part) -> int {
+  auto cmi_branch = [&]() -> int {
     if (dbg_skip & 1) return MIMRL_OK;
     StreamGuard g(this, S(5));
-    if (part & 1) {
-      bf16 = bf_fwd;
-      MX(cmi_forward(stage, want_grad));
-      if (imgT_pending && !imgT_late) MX(imgT_launch());
-      MX(dbg_delay(stream, stage == 1 ? 4 : 14));
+    bf16 = bf_fwd;
+    MX(cmi_forward(stage, want_grad));
+    if (imgT_pending) {   // side 3 already waits for the stage boundary (fork above); only the launch was held back
+      imgT_pending = false;
+      MX(frag_tr_launch(side[3]));
+      if (!dbg_skip_imgt) MX(bf16_transposed_images(side[3], bufs.crit_p, crit_imgT, ttab));
     }
+    MX(dbg_delay(stream, stage == 1 ? 4 : 14));
     // (no helper side stream for this branch's weight gradients: it runs on side 5, and a fork / join pair hanging off a captured stream
     //  other than the capture's origin sends this HIP runtime's EndCapture into an endless recursion -- tried, core dump)
-    if ((part & 2) && backward) { bf16 = bf_bwd; if (imgT_ready && !(skip_imgT_refresh && stage == 1)) MX(chain(5, 3)); MX(cmi_backward(stage)); MX(dbg_delay(stream, stage == 1 ? 6 : 16)); }
+    if (backward) { bf16 = bf_bwd; if (imgT_ready && !(skip_imgT_refresh && stage == 1)) MX(chain(5, 3)); MX(cmi_backward(stage)); MX(dbg_delay(stream, stage == 1 ? 6 : 16)); }
     return MIMRL_OK;
   };
-  auto mi_branch = [&](int part) -> int {
+  auto mi_branch = [&]() -> int {
     if (dbg_skip & 2) return MIMRL_OK;
-    if (part & 1) {
-      bf16 = bf_fwd;
-      { Scope sc(this, MIMRL_PH_EST_FWD); MX(mi_forward(stage, want_grad)); }
-      MX(dbg_delay(stream, stage == 1 ? 3 : 15));
-    }
-    if ((part & 2) && backward) {
+    bf16 = bf_fwd;
+    { Scope sc(this, MIMRL_PH_EST_FWD); MX(mi_forward(stage, want_grad)); }
+    MX(dbg_delay(stream, stage == 1 ? 3 : 15));
+    if (backward) {
       bf16 = bf_bwd;
       if (imgT_ready && !(skip_imgT_refresh && stage == 1)) MX(join(3, 3));
       Scope sc(this, MIMRL_PH_EST_BWD);
@@ -587,19 +565,10 @@ int mimrl_handle::estimators_all(int stage, bool want_grad, bool backward) {
     }
     return MIMRL_OK;
   };
-  // capture order of the two branches (graph nodes are dispatched in capture order; bit 0: stage 1, bit 1: stage 2 -> MI first)
-  constexpr int mi_first = 0;
-  // round 5b: both FORWARD halves are captured in front of either backward half (bit mask like mi_first; default: stage 2).  With the stage
-  // boundary inside the critic update both branches hang off the update node directly, and with a whole branch captured first the other
-  // branch's first kernel landed on a hardware queue BEHIND the first branch's weight-gradient launch (head-of-line: 49 us late).
-  if ((interleave >> (stage - 1)) & 1) {
-    if ((mi_first >> (stage - 1)) & 1) { MX(mi_branch(1)); MX(cmi_branch(1)); }
-    else { MX(cmi_branch(1)); MX(mi_branch(1)); }
-    if (imgT_pending) MX(imgT_launch());
-    if ((mi_first >> (stage - 1)) & 1) { MX(mi_branch(2)); MX(cmi_branch(2)); }
-    else { MX(cmi_branch(2)); MX(mi_branch(2)); }
-  } else if ((mi_first >> (stage - 1)) & 1) { MX(mi_branch(3)); MX(cmi_branch(3)); }
-  else { MX(cmi_branch(3)); MX(mi_branch(3)); }
+  // capture order of the two branches (graph nodes are dispatched in capture order): the whole CMI branch, then the whole MI branch
+  // (MI first, or both forward halves in front of either backward half: DESIGN.md section 7)
+  MX(cmi_branch());
+  MX(mi_branch());
   bf16 = bf_fwd;
   if (!multi_stream) return MIMRL_OK;
   return join(5, 5);

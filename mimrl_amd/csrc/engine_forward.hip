@@ -87,7 +87,6 @@ int mimrl_handle::encoders_forward(bool save, int knn_stage) {
       PrecGuard pg(this, fp32_site(2));
       MX(G_on(stream, gd));
       }
-      if (pending_text && pending_text_at == 1) { MX(pending_text()); pending_text = nullptr; }
     }
     for (int m = 0; m < 2; ++m) {
       a.lens[m] = lens[m];
@@ -126,7 +125,6 @@ int mimrl_handle::encoders_forward(bool save, int knn_stage) {
       MX(dbg_delay(S(4), 11));
     }
     { Scope sc(this, MIMRL_PH_GRU_FWD); MX(gru_forward(stream, a, (prec & MIMRL_PREC_BF16_GRU_FWD) != 0)); }
-    if (l == 0 && pending_text && pending_text_at == 2) { MX(pending_text()); pending_text = nullptr; }
     MX(dbg_delay(stream, 1));
   }
   return MIMRL_OK;
@@ -237,27 +235,19 @@ int mimrl_handle::model_forward(bool train, bool save, int knn_stage, int part) 
     // text branch (side 0): W_t projection (Model.py:395) + dropout -> cube slot 0.  Captured BEFORE the encoders although it
     // has slack until the tail starts: graph nodes start in capture order, and a branch captured behind the two GRU layers is
     // dispatched behind them too and then delays the tail (measured: 1.46 vs 1.34 ms).
-    // (default since round 4 -- with the kNN sampler's two launches on side 4 the scan there delayed the layer-0 input projection:
-    //  cfg2 0.840 -> 0.829 ms, cfg3 6.97 -> 6.87; MIMRL_LENS_SIDE0=0 puts it back)
-    constexpr bool prefix_split = true;   // (an environment knob until round 5: fixed at its measured optimum)
-    if (prefix_split && cfg.encoder == MIMRL_ENCODER_GRU && side_on(0)) {
+    // (since round 4 -- with the kNN sampler's two launches on side 4 the scan there delayed the layer-0 input projection:
+    //  cfg2 0.840 -> 0.829 ms, cfg3 6.97 -> 6.87)
+    if (cfg.encoder == MIMRL_ENCODER_GRU && side_on(0)) {
       // lengths (Model.py:425-432): only the recurrence needs them.  Side 0 has slack (the text projection is needed at the tail);
       // on side 4 the scan sat in front of the video input projection, the longest chain ahead of the layer-0 recurrence
       MX(seq_lengths2(S(0), bufs.audio, cfg.d_a, lens[0], bufs.video, cfg.d_v, lens[1], B, T));
       MX(next_event(&ev_lens));
       HIPX(hipEventRecord(ev_lens, S(0)));
     }
-    constexpr int text_late = 0;   // (an environment knob until round 5: fixed at its measured optimum)
-    auto text_branch = [this, BT_, D, part, fused_pre, B, T, L, pdrop]() -> int {
-      { PrecGuard pg(this, fp32_site(1)); GemmDesc g = gemm_nt(bufs.text, cfg.d_t, P(w_t), cfg.d_t, tx_raw, D, (int)BT_, D, cfg.d_t); g.f16 = fwd_f16; MX(G_on(S(0), g)); }
-      MX(dbg_delay(S(0), 10));
-      if (part == 0 && !fused_pre) MX(text_post_fwd(S(0), tx_raw, cube0, B, T, L, 3, D, 0, pdrop[0], key(), 0));
-      return MIMRL_OK;
-    };
-    if (text_late && cfg.encoder == MIMRL_ENCODER_GRU && l0_packed) { pending_text = text_branch; pending_text_at = text_late; }
-    else MX(text_branch());
+    { PrecGuard pg(this, fp32_site(1)); GemmDesc g = gemm_nt(bufs.text, cfg.d_t, P(w_t), cfg.d_t, tx_raw, D, (int)BT_, D, cfg.d_t); g.f16 = fwd_f16; MX(G_on(S(0), g)); }
+    MX(dbg_delay(S(0), 10));
+    if (part == 0 && !fused_pre) MX(text_post_fwd(S(0), tx_raw, cube0, B, T, L, 3, D, 0, pdrop[0], key(), 0));
     MX(encoders_forward(save, knn_stage));
-    if (pending_text) { MX(pending_text()); pending_text = nullptr; }
     MX(join(0, 0));
     if (part == 1) return MIMRL_OK;
   } else if (!fused_pre && !pre_done) {

@@ -11,47 +11,24 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
   if (!keep_events) ev_next = 0;
   if (stage == 1) {
     static const bool no_share = knob("MIMRL_NO_SHARED_PREFIX") != nullptr;   // tuning knob: evaluate the prefix twice
-    constexpr bool prefix_split = false;   // (an environment knob until round 5: fixed at its measured optimum)
     const bool share = prefetch && !no_share;
-    // counters + scalar reset: the first consumers are the kNN sampler and the recurrence, both behind the join of side 4 in
-    // encoders_forward -- in the shared-prefix step it runs on side 4 beside the input projections instead of in front of them
-    const bool begin_on_side = share && have_banks && skip_zero && prefix_split && multi_stream && cfg.encoder == MIMRL_ENCODER_GRU;
-    if (begin_on_side) MX(fork(4, 4));
+    // counters + scalar reset: the first consumers are the kNN sampler and the recurrence.
     // shared-prefix step with packed layer-0 operands: the pack launch is the first kernel of the prefix on this stream and nothing in
     // front of the recurrence reads the counters or the scalars -- the bookkeeping rides on it (one launch + one gap less on the chain)
-    // (measured neutral, 0.970 vs 0.966 ms: the single-thread kernel hides in the gap between two graph launches -- opt-in)
-    // (round 4, with the length scan on side 0: -4 us on average over four alternating runs, cfg3 neutral -- on by default; =0: the separate kernel)
-    constexpr bool want_begin_in_pack = true;   // (an environment knob until round 5: fixed at its measured optimum)
-    begin_in_pack = want_begin_in_pack && share && have_banks && skip_zero && !begin_on_side && l0_packed && cfg.encoder == MIMRL_ENCODER_GRU;
+    // (first measured neutral, 0.970 vs 0.966 ms: the single-thread kernel hides in the gap between two graph launches;
+    //  round 4, with the length scan on side 0: -4 us on average over four alternating runs, cfg3 neutral)
+    begin_in_pack = share && have_banks && skip_zero && l0_packed && cfg.encoder == MIMRL_ENCODER_GRU;
     if (!begin_in_pack) {
-      launch_begin_stage(begin_on_side ? side[4] : stream, d_ints, have_banks ? d_ints + 2 : nullptr,
-                         bufs.scalars, 0, 32);
+      launch_begin_stage(stream, d_ints, have_banks ? d_ints + 2 : nullptr, bufs.scalars, 0, 32);
       LAUNCH_CHECK();
     }
     if (!have_banks) return MIMRL_OK;
     if (!skip_zero) HIPX(hipMemsetAsync(bufs.crit_g, 0, sizeof(float) * layout.floats[MIMRL_GROUP_CRITIC], stream));   // epoch-0 rule: zero loss, no update (Customization.py:97-98, Solver.py:201-203)
     bf16 = (prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
-    constexpr bool pre_first = false;   // (an environment knob until round 5: fixed at its measured optimum): capture order of the two chains
-    auto issue_prefetch = [&](hipEvent_t e) -> int {
-      // the stage-2 forward pass of this batch depends on nothing stage 1 changes: one sequential branch on its own
-      // stream, into the primary buffers (stage 1 itself works on the alternate set)
-      HIPX(hipStreamWaitEvent(pre_stream, e, 0));
-      const bool ms = multi_stream;
-      const unsigned sm = side_mask;
-      int r;
-      {
-        StreamGuard g(this, pre_stream);
-        multi_stream = false; rng_add = 1;     // begin_stage(2) has not run yet: use the dropout key it will produce
-        r = model_forward(true, true, 0);
-        multi_stream = ms; rng_add = 0; side_mask = sm;
-      }
-      return r;
-    };
     hipEvent_t e_begin = nullptr;
     if (prefetch) {
       MX(next_event(&e_begin));
       HIPX(hipEventRecord(e_begin, stream));
-      if (pre_first && !share) MX(issue_prefetch(e_begin));
       if (!share) swap_fwd_set();
     }
     int r1;
@@ -115,7 +92,21 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
     if (r1 == 0) r1 = estimators_all(1, true, true);
     if (prefetch) swap_fwd_set();
     MX(r1);
-    if (prefetch && !share && !pre_first) MX(issue_prefetch(e_begin));
+    if (prefetch && !share) {
+      // the stage-2 forward pass of this batch depends on nothing stage 1 changes: one sequential branch on its own
+      // stream, into the primary buffers (stage 1 itself works on the alternate set); captured behind stage 1's own chain
+      HIPX(hipStreamWaitEvent(pre_stream, e_begin, 0));
+      const bool ms = multi_stream;
+      const unsigned sm = side_mask;
+      int r;
+      {
+        StreamGuard g(this, pre_stream);
+        multi_stream = false; rng_add = 1;     // begin_stage(2) has not run yet: use the dropout key it will produce
+        r = model_forward(true, true, 0);
+        multi_stream = ms; rng_add = 0; side_mask = sm;
+      }
+      MX(r);
+    }
     if (!fuse_boundary) {
       launch_finalize_stage1(stream, bufs.scalars, mi_raw, cmi_raw, bce_raw, coef1());
       LAUNCH_CHECK();
@@ -225,7 +216,6 @@ int mimrl_handle::enqueue_apply(int stage) {
   MX(adam_step(stream, a, task_loss));
   if (have_frag) {
     // combined step: beside the stage boundary on side 3 (the stage-2 estimators join it before their first stack)
-    constexpr bool inline_frag = false;   // (an environment knob until round 5: fixed at its measured optimum)
     FragTable ft = ftab;
     if (fwd_in_adam) {   // only the data-gradient entries are left for the launch
       ft.n = 0;
@@ -240,8 +230,8 @@ int mimrl_handle::enqueue_apply(int stage) {
       // (fwd_in_adam: not even the launch happens here -- as the update's FIRST captured child it would keep the update's hardware queue and
       //  push the stage-2 estimators' first kernels onto other queues, 21 us behind the update; estimators_all issues it on side 3 in front
       //  of the transposed-image refresh, in capture order behind the forward stacks)
-      if (fwd_in_adam && fuse_boundary && side_on(3) && !inline_frag) { ftab_tr = ft; frag_tr_deferred = true; }
-      else if (fuse_boundary && side_on(3) && !inline_frag) { MX(fork(3, 3)); MX(bf16_frag_images(side[3], bufs.crit_p, crit_frag, ft)); frag_side_pending = true; }
+      if (fwd_in_adam && fuse_boundary && side_on(3)) { ftab_tr = ft; frag_tr_deferred = true; }
+      else if (fuse_boundary && side_on(3)) { MX(fork(3, 3)); MX(bf16_frag_images(side[3], bufs.crit_p, crit_frag, ft)); frag_side_pending = true; }
       else MX(bf16_frag_images(stream, bufs.crit_p, crit_frag, ft));
     }
   }
@@ -526,7 +516,7 @@ int mimrl_handle::run_fwd2_tail() {
 
 // Captured-graph diagnostics: MIMRL_GRAPH_DOT=<file> dumps the captured two-stage step (hipGraphDebugDotPrint: kernel names, edges).
 // (Rounds 4-5 also re-inserted fork edges here -- by height, captured-stream-first, pad nodes, a searched permutation: the captured order
-// was a local optimum of all of them; the machinery went in round 6, git keeps it.)
+// was a local optimum of all of them; the machinery was removed in round 6, git keeps it.)
 static int graph_postprocess(hipGraph_t g) {
   static const char* dot = knob("MIMRL_GRAPH_DOT");
   if (dot) HIPX(hipGraphDebugDotPrint(g, dot, hipGraphDebugDotFlagsVerbose));
@@ -552,12 +542,11 @@ int mimrl_handle::run_step() {
   hipGraphExec_t& ex = GS().graph[0][0];
   if (ex && GS().rows[0][0] != bank_rows) retire(ex);   // bank size is baked into the kernel arguments
   if (!ex) {
-    constexpr bool no_boundary = false;   // (an environment knob until round 5: fixed at its measured optimum): the round-1 stage boundary
     hipGraph_t g = nullptr;
     if (!cap_stream) HIPX(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
     HIPX(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
     stream = cap_stream;
-    fuse_boundary = !no_boundary; skip_imgT_refresh = use_imgT && !no_boundary; wtT_prebuilt = bf_bwd && fused_cube_bwd && !no_boundary;
+    fuse_boundary = true; skip_imgT_refresh = use_imgT; wtT_prebuilt = bf_bwd && fused_cube_bwd;
     wtT_built = false;
     int r = enqueue_grads(1, true);
     if (r == 0) r = reduce_bucket(1);

@@ -818,8 +818,7 @@ static bool plain_accumulate(const GemmDesc& d) {
 
 // fast-path eligibility and tile shape; returns false when the generic kernel has to take the GEMM
 static bool fast_plan(const GemmDesc& d, bool bf16, GemmPlan* p) {
-  constexpr int no_fast = 0;   // (MIMRL_GEMM_NO_FAST went in round 6: the parametrised knob test found it BROKEN in bf16 mode -- bf16-stored operands exist on the fast path only)
-  if (!bf16 || no_fast) return false;
+  if (!bf16) return false;   // (bf16-stored operands exist on the fast path only: there is no switch that turns it off)
   const int ca = fast_class(d.A, d.sa_m, d.sa_k, d.sa_b, d.sa_bo, d.M, d.K, d.a_bf16, d.a_pad4), cb = fast_class(d.B, d.sb_n, d.sb_k, d.sb_b, d.sb_bo, d.N, d.K, d.b_bf16);
   if (!ca || !cb || (ca == 2 && cb == 1)) return false;
   if (d.A2 && (fast_class(d.A2, d.sa2_m, d.sa2_k, d.sa2_b, 0, d.M, d.K2, d.a_bf16) != ca || fast_class(d.B2, d.sb2_n, d.sb2_k, d.sb2_b, 0, d.N, d.K2, d.b_bf16) != cb))
@@ -846,21 +845,10 @@ static bool fast_plan(const GemmDesc& d, bool bf16, GemmPlan* p) {
     const int tm = cand[c][0], tn = cand[c][1];
     if (d.M < 64 * tm || d.N < 64 * tn) continue;
     const long t = tiles(tm, tn);
-    constexpr long min_wgs = 700;   // (an environment knob until round 5: fixed at its measured optimum).  Round 3b: 224 -> 700 (cfg2, 4 interleaved runs each: 0.906-0.912 -> 0.886-0.901 ms; 1000 / 1250 the same): a workgroup is a serial prologue - loop - epilogue and a CU overlaps them only ACROSS workgroups, so ~3 per CU beat ~2 larger ones
+    constexpr long min_wgs = 700;   // Round 3b: 224 -> 700 (cfg2, 4 interleaved runs each: 0.906-0.912 -> 0.886-0.901 ms; 1000 / 1250 the same): a workgroup is a serial prologue - loop - epilogue and a CU overlaps them only ACROSS workgroups, so ~3 per CU beat ~2 larger ones
     // (not for split-K accumulations over a long reduction: at cfg3's K = 128,000 rows smaller tiles mean more splits and more atomics,
     //  7.11 -> 7.52 ms with 700 for all)
     if (t * split(t) >= ((acc && ktiles > 1024) ? 224 : min_wgs) || c == 2) { pick = c; break; }
-  }
-  // round 5b: weight gradients over a LONG reduction with both operands 16-bit stored and N a multiple of 256 (dW_ih of GRU layer 1:
-  // [384 x 256] per direction over B * T rows) take 128 x 256 tiles -- every row of A (dg: the larger operand) is then read by ONE workgroup
-  // instead of two; the split-K chunks of a 128 x 128 grid drift apart in time and their re-reads miss the 4 MB L2 (1.39 GB fetched for 0.66)
-  constexpr int wide_n = 0;   // (an environment knob until round 5: fixed at its measured optimum): 1 all, 2 M % 256 == 0 only, 3 the others only
-  const bool wide = wide_n && (wide_n == 1 || (wide_n == 2) == (d.M % 256 == 0)) && acc && ktiles > 1024 && ca == 2 && cb == 2 && d.a_bf16 && d.b_bf16 && d.N % 256 == 0 && d.M >= 128;
-  if (wide) {
-    p->fast = 1; p->tm = 2; p->tn = 4; p->ca = ca; p->cb = cb;
-    p->tiles = tiles(2, 4); p->nsplit = split(p->tiles); p->kt_per = (ktiles + p->nsplit - 1) / p->nsplit;
-    p->variant = 24;
-    return true;
   }
   p->fast = 1; p->tm = cand[pick][0]; p->tn = cand[pick][1]; p->ca = ca; p->cb = cb;
   p->tiles = tiles(p->tm, p->tn);
@@ -873,18 +861,15 @@ static bool fast_plan(const GemmDesc& d, bool bf16, GemmPlan* p) {
 void gemm_plan(const GemmDesc& d, bool bf16, GemmPlan* p) {
   p->fast = 0; p->tm = p->tn = 1; p->ca = p->cb = 0;
   if (fast_plan(d, bf16, p)) return;
-  constexpr int no_lean = 0;   // (an environment knob until round 5: fixed at its measured optimum)
-  constexpr int no_big = 0;
   const bool va = vec_ok_a(d.A, d.sa_m, d.sa_k, d.sa_b) && d.sa_bo % 4 == 0, vb = vec_ok_b(d.B, d.sb_k, d.sb_n, d.sb_b) && d.sb_bo % 4 == 0;
   const bool va2 = d.A2 ? vec_ok_a(d.A2, d.sa2_m, d.sa2_k, d.sa2_b) : true, vb2 = d.B2 ? vec_ok_b(d.B2, d.sb2_k, d.sb2_n, d.sb2_b) : true;
   // lean = 16-byte loads only.  Ragged M / N are fine for k-contiguous operands (rows are clamped in the loader).
   const bool a_kfast = d.sa_k == 1 && (!d.A2 || d.sa2_k == 1), b_kfast = d.sb_k == 1 && d.sb_n != 1 && (!d.B2 || (d.sb2_k == 1 && d.sb2_n != 1));
-  constexpr int no_ragged = 0;
-  const bool lean = bf16 && !no_lean && (d.M % BM == 0 || (a_kfast && !no_ragged)) && (d.N % BN == 0 || (b_kfast && !no_ragged)) &&
+  const bool lean = bf16 && (d.M % BM == 0 || a_kfast) && (d.N % BN == 0 || b_kfast) &&
                     va && vb && va2 && vb2 && d.K >= 64;
   const long tiles = (long)((d.N + BN - 1) / BN) * ((d.M + BM - 1) / BM) * d.batch;
   // small grids gain nothing from occupancy: stage 128 k-values per round trip (one-shot for K <= 128)
-  const bool lean128 = lean && !no_big && tiles <= 256 && d.K >= 128 && (!d.A2 || d.K2 >= 64);
+  const bool lean128 = lean && tiles <= 256 && d.K >= 128 && (!d.A2 || d.K2 >= 64);
   p->variant = !bf16 ? 0 : lean128 ? 3 : lean ? 2 : 1;
   const int BKh = lean128 ? 128 : (lean ? 64 : 32);
   const int ktiles = (d.K + BKh - 1) / BKh;
@@ -900,8 +885,7 @@ void gemm_plan(const GemmDesc& d, bool bf16, GemmPlan* p) {
 }
 
 int gemm_group(hipStream_t s, const GemmDesc* ds, int n, bool bf16) {
-  constexpr int no_group = 0;   // (an environment knob until round 5: fixed at its measured optimum)
-  bool ok = bf16 && !no_group && n >= 2 && n <= GEMM_GROUP_MAX;
+  bool ok = bf16 && n >= 2 && n <= GEMM_GROUP_MAX;
   int ca = 0, cb = 0;
   long total = 0;
   for (int i = 0; ok && i < n; ++i) {
@@ -933,8 +917,7 @@ int gemm_group(hipStream_t s, const GemmDesc* ds, int n, bool bf16) {
 }
 
 int gemm_group_splitk(hipStream_t s, const GemmDesc* ds, int n, bool bf16) {
-  constexpr int no_group = 0;   // (an environment knob until round 5: fixed at its measured optimum)
-  bool ok = bf16 && !no_group && n >= 2 && n <= GEMM_GROUPK_MAX;
+  bool ok = bf16 && n >= 2 && n <= GEMM_GROUPK_MAX;
   int ca = 0, cb = 0;
   long tiles = 0;
   double macs = 0;
@@ -1019,8 +1002,7 @@ int gemm(hipStream_t s, const GemmDesc& d, bool bf16) {
   ka.vec_b = vec_ok_b(d.B, d.sb_k, d.sb_n, d.sb_b) && d.sb_bo % 4 == 0;
   ka.vec_a2 = d.A2 ? vec_ok_a(d.A2, d.sa2_m, d.sa2_k, d.sa2_b) : 1;
   ka.vec_b2 = d.B2 ? vec_ok_b(d.B2, d.sb2_k, d.sb2_n, d.sb2_b) : 1;
-  constexpr int no_xcd = 0;   // (an environment knob until round 5: fixed at its measured optimum)
-  ka.xcd_remap = !no_xcd;
+  ka.xcd_remap = 1;
   static const int dbg_gemm = dbg_env("MIMRL_DBG_GEMM") ? atoi(dbg_env("MIMRL_DBG_GEMM")) : 0;
   ka.dbg = dbg_gemm;
   ka.ksplit = pl.nsplit;
@@ -1060,10 +1042,6 @@ int gemm(hipStream_t s, const GemmDesc& d, bool bf16) {
     case 18: FASTK(1, 1, true, true);
     case 19: FASTB(1, 1, true, false);
     case 20: FASTB(1, 1, false, false);
-    case 24:   // 128 x 256 tiles, (RC,RC), both operands 16-bit stored (fast_plan: wide)
-      if (d.b_f16cvt) hipLaunchKernelGGL((gemm_fast_bfh_kernel<2, 4>), grid, dim3(256), 0, s, ka);
-      else hipLaunchKernelGGL((gemm_fast_bf_kernel<2, 4, false, false, true>), grid, dim3(256), 0, s, ka);
-      break;
     case 0: GENK(false, 32, false);
     case 3: GENK(true, 128, true);
     case 2: GENK(true, 64, true);

@@ -891,8 +891,6 @@ long gru_saved_floats(int B, int T) {
 }
 
 int gru_pick_btv(int B, int nmod) {
-  constexpr int force = 0;   // (an environment knob until round 5: fixed at its measured optimum)
-  if (force >= 1 && force <= BR) return force;
   int btv = (B * nmod * 2 + 127) / 128;      // ~128 workgroups (measured best at B=128: 4 rows per workgroup)
   if (btv < 1) btv = 1;
   if (btv > BR) btv = BR;

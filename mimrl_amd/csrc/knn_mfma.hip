@@ -567,7 +567,7 @@ KnnPlan knn_plan(int N, int m, int k) {
   p.NTW = (NT + p.S - 1) / p.S;
   p.RP = 4 / p.S;
   const int pairs = (N + 31) / 32;
-  constexpr int target = 512;   // (an environment knob until round 5: fixed at its measured optimum): workgroups per launch
+  constexpr int target = 512;   // workgroups per launch
   int ppw = (int)(((long)pairs * std::max(nwide, 1) * p.nab + (long)p.RP * target - 1) / ((long)p.RP * target));
   ppw = std::max(1, std::min(ppw, MAXW / p.RP));
   p.ppw = ppw;
@@ -602,10 +602,9 @@ int knn_sample(hipStream_t s, const KnnArgs& a, void* scratch, size_t scratch_by
   const size_t shb = mask_b + AT * 256 * sizeof(float) + AT * 256 * (size_t)K * (sizeof(float) + sizeof(int));   // exact-scan kernel
   if (shb > 150 * 1024) return set_error(MIMRL_ERR_ARG, "knn: bank too large for the LDS bitmask (N=%d)", a.N);
   const dim3 mgrid((a.m + AT - 1) / AT, a.ncall);
-  constexpr bool force_brute = false;   // (MIMRL_KNN_BRUTE went in round 6: the exact scan stays the path of k > 4 / odd widths, held to the host brute force by test_knn_matches_exact_bruteforce)
-  // k > 4 (no BASELINE configuration; the reference's default is k = 2): the exact scan -- a k + 2 = 10-deep register list per lane and
+  // odd feature widths and k > 4: the exact scan (held to the host brute force by test_knn_matches_exact_bruteforce).  k > 4 (no BASELINE configuration; the reference's default is k = 2): the exact scan -- a k + 2 = 10-deep register list per lane and
   // tile makes the tile kernel's epilogue the bottleneck (and costs minutes of compile time)
-  if (generic || force_brute || a.k > 4) {
+  if (generic || a.k > 4) {
     if (shb > 64 * 1024) {   // (k > 4: 64 KiB of candidate lists alone)
       const void* f = K == 2 ? reinterpret_cast<const void*>(knn_brute_kernel<2>) : K == 4 ? reinterpret_cast<const void*>(knn_brute_kernel<4>)
                                                                                            : reinterpret_cast<const void*>(knn_brute_kernel<8>);

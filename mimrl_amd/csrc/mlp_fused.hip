@@ -988,8 +988,6 @@ bool mlp_fused_supported(int nb, int rows, int nl, const int* dims) {
 // few workgroups (latency-bound stack): the 8-wave kernel with the register-resident, prefetched weight tile.  Every reduction
 // width must be a whole number of 8-element pieces (16-byte loads) or < 16 (the FMA path).
 static int mlp_small8(const MlpFusedArgs& a, bool bwd) {   // -> 0 (use the 4-wave kernel), or the register chunks needed: 4 / 6
-  constexpr int waves = 0;   // (an environment knob until round 5: fixed at its measured optimum): 4 = never, 8 = both directions
-  if (waves == 4) return 0;
   const long wgs = (long)((a.rows + RT - 1) / RT) * a.nb;
   if (wgs > 512) return 0;
   int kmax = 0;

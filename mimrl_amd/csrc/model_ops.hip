@@ -1212,7 +1212,7 @@ int kmix_fwd(hipStream_t s, const float* x, float* z, KMixW w, long R, int D) {
 int kmix_bwd(hipStream_t s, const float* x, const float* dz, float* dx, KMixW w, long R, int D) {
   if (w.ik > KM || w.hk > KM || w.ok > KM) return set_error(MIMRL_ERR_ARG, "kmix: K-axis sizes must be <= %d", KM);
   const int mx = w.ik > w.hk ? (w.ik > w.ok ? w.ik : w.ok) : (w.hk > w.ok ? w.hk : w.ok);
-  constexpr int wgs = 512;   // (an environment knob until round 5: fixed at its measured optimum)
+  constexpr int wgs = 512;
   const bool exact3 = w.ik == 3 && w.hk == 3 && w.ok == 3 && !w.ln_first && w.drop_p <= 0.f;
   if (exact3) hipLaunchKernelGGL((kmix_bwd_kernel<3, 0, true>), dim3(grid_for(R * D, 256, wgs)), dim3(256), 0, s, x, dz, dx, w, R, D);
   else if (mx <= 3) hipLaunchKernelGGL((kmix_bwd_kernel<3, 0>), dim3(grid_for(R * D, 256, wgs)), dim3(256), 0, s, x, dz, dx, w, R, D);
@@ -1227,19 +1227,18 @@ int kmix_bwd_part(hipStream_t s, const float* x, const float* dz, float* dx, KMi
   if (w.ik > KM || w.hk > KM || w.ok > KM) return set_error(MIMRL_ERR_ARG, "kmix: K-axis sizes must be <= %d", KM);
   const int mx = w.ik > w.hk ? (w.ik > w.ok ? w.ik : w.ok) : (w.hk > w.ok ? w.hk : w.ok);
   if (part == 1) {
-    constexpr int dx_wgs = 4096;   // (an environment knob until round 5: fixed at its measured optimum)
+    constexpr int dx_wgs = 4096;
     const dim3 grid(grid_for(R * D, 256, dx_wgs));
     if (mx <= 3) hipLaunchKernelGGL((kmix_bwd_kernel<3, 1>), grid, dim3(256), 0, s, x, dz, dx, w, R, D);
     else if (mx <= 4) hipLaunchKernelGGL((kmix_bwd_kernel<4, 1>), grid, dim3(256), 0, s, x, dz, dx, w, R, D);
     else hipLaunchKernelGGL((kmix_bwd_kernel<8, 1>), grid, dim3(256), 0, s, x, dz, dx, w, R, D);
   } else {
-    // workgroup count (tuning knob).  The kernel is ~33 us of fixed cost (weight staging, 64 wave reductions, LDS and global
+    // workgroup count.  The kernel is ~33 us of fixed cost (weight staging, 64 wave reductions, LDS and global
     // atomics) + ~25 us of element work at cfg2; 256 workgroups is the measured optimum (128: 67 us, 256: 53 us, 512: 75 us).  A
     // two-level reduction through scratch slots with a last-arriver finisher was tried and lost (the __threadfence it needs is an
     // L2 write-back on this multi-XCD part: 157 us).
     constexpr int pg_wgs = 256;
-    const int cap = pg_wgs > 0 ? pg_wgs : 256;
-    const dim3 grid(grid_for(R * D, 256, cap));
+    const dim3 grid(grid_for(R * D, 256, pg_wgs));
     if (mx <= 3) hipLaunchKernelGGL((kmix_bwd_kernel<3, 2>), grid, dim3(256), 0, s, x, dz, dx, w, R, D);
     else if (mx <= 4) hipLaunchKernelGGL((kmix_bwd_kernel<4, 2>), grid, dim3(256), 0, s, x, dz, dx, w, R, D);
     else hipLaunchKernelGGL((kmix_bwd_kernel<8, 2>), grid, dim3(256), 0, s, x, dz, dx, w, R, D);
