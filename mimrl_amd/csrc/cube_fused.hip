@@ -21,7 +21,7 @@
 // Everything the (unfused) backward pass needs is written out in fp32 with the unfused path's layouts.
 #include "cube_fused.h"
 
-#include "kmix_device.h"
+#include "cube_bookends.h"
 
 #include <type_traits>
 
@@ -142,8 +142,11 @@ __host__ __device__ inline Carve carve(int K, int nmt, int G) {
 // every LDS / global round trip and every VALU dependency chain of the epilogues is exposed.  G = 2: the groups take alternate column
 // slabs in phase L (own B-images and staging tiles), interleave the (l, d) pairs of phase K, and each owns one 64-column half of the
 // D-axis outputs (own weight-image buffers: 6 stagings per group instead of 12 in a row).
-template <bool SAVE, int NMT, int G>
-__global__ __launch_bounds__(256 * G) void cube_fwd_fused_kernel(CubeFusedArgs a) {
+// PRE: the tile comes from the encoder outputs (CubePre) -- set-up section.  HEAD: the head reduction follows the LayerNorm(D) epilogue (CubeHead).
+template <bool SAVE, int NMT, int G, bool PRE, bool HEAD>
+__device__ __forceinline__ void cube_fwd_fused_body(const CubeFusedArgs& a) {
+  static_assert(!(PRE || HEAD) || G == 2, "PRE / HEAD: 8 waves (12 time-phase streams on 8 waves; head_fwd_kernel's 512-thread shape)");
+  static_assert(!HEAD || NMT == 1, "HEAD: every row of the block output in the one LDS tile");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NT = 256 * G;
   const int tid = threadIdx.x, grp = tid >> 8, t = tid & 255, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
@@ -178,6 +181,94 @@ __global__ __launch_bounds__(256 * G) void cube_fwd_fused_kernel(CubeFusedArgs a
       pr[3] = tid < ol ? a.l_be[tid] : 0.f;
     }
     CPHASE(13);
+    if constexpr (PRE) {
+      // The tile from its sources (K == 3, C == 384).  A (slot, t mod 4) stream of rows belongs to ONE wave, which walks it in increasing t: the
+      // temporal means keep tail_pre_kernel's summation order.  12 streams on 8 waves: waves 0..3 take text + video of phase w, waves 4..7 audio
+      // of phase w - 4 (a text row is two loads and a multiply).  T <= 64: at most 16 rows per stream -- every text row and the first 8
+      // encoder rows are requested together with the weights above, the remaining encoder rows in a second batch.  Loads are unconditional
+      // from clamped rows (the audio waves request the text rows too and drop them: a branch around loads waits for everything in flight).
+      const CubePre& pp = a.pre;
+      const int T = pp.T, w8 = tid >> 6, ph = w8 & 3, ln64 = tid & 63;
+      const bool audio = w8 >= 4;
+      const int m = audio ? 0 : 1, slot = 1 + m;
+      const uint32_t rstep = (uint32_t)(*pp.key.step + pp.key.add);   // once (see drop_scale_at)
+      const float* __restrict__ txb = pp.tx_raw + (long)b * T * D;
+      // (selected, not indexed: a run-time index into the kernel arguments would copy them to scratch)
+      const float* __restrict__ h2 = (audio ? pp.h2[0] : pp.h2[1]) + (long)b * T * 2 * D;
+      const float* __restrict__ gam = audio ? pp.gamma[0] : pp.gamma[1];
+      const float* __restrict__ bet = audio ? pp.beta[0] : pp.beta[1];
+      float* __restrict__ lmean = audio ? pp.mean[0] : pp.mean[1];
+      float* __restrict__ lrstd = audio ? pp.rstd[0] : pp.rstd[1];
+      const float ga0 = gam[ln64], ga1 = gam[ln64 + 64], be0 = bet[ln64], be1 = bet[ln64 + 64];
+      const float pdrop = audio ? pp.p[1] : pp.p[2];
+      const bool wr = pp.cube != nullptr;                             // (kernel argument: uniform)
+      float xt[16][2], v[8][2];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int tt = ph + 4 * q < T ? ph + 4 * q : T - 1;
+        xt[q][0] = txb[(long)tt * D + ln64]; xt[q][1] = txb[(long)tt * D + ln64 + 64];
+      }
+      float at0 = 0.f, at1 = 0.f, al0 = 0.f, al1 = 0.f;
+      auto ln_load = [&](int q0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int tt = ph + 4 * (q0 + q) < T ? ph + 4 * (q0 + q) : T - 1;
+          const float* hr = h2 + (long)tt * 2 * D;
+          v[q][0] = hr[ln64] + hr[D + ln64]; v[q][1] = hr[ln64 + 64] + hr[D + ln64 + 64];
+        }
+      };
+      auto ln_rows = [&](int q0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int tt = ph + 4 * (q0 + q);
+          if (tt < T) {                                               // (wave-uniform)
+            const long r = (long)b * T + tt;
+            float mu, rs, y0, y1;
+            pre_ln_row(v[q][0], v[q][1], ga0, ga1, be0, be1, pdrop, pp.key, rstep, (uint32_t)slot, r, ln64, mu, rs, y0, y1);
+            if (wr) {
+              if (ln64 == 0) { lmean[r] = mu; lrstd[r] = rs; }
+              float* out = pp.cube + (((long)b * il + tt) * 3 + slot) * D;
+              out[ln64] = y0; out[ln64 + 64] = y1;
+            }
+            Xm[tt * XP + slot * D + ln64] = to_f16_sat(y0); Xm[tt * XP + slot * D + ln64 + 64] = to_f16_sat(y1);
+            al0 += y0; al1 += y1;
+          }
+        }
+      };
+      ln_load(0);
+      if (!audio) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int tt = ph + 4 * q;
+          if (tt < T) {
+            const long r = (long)b * T + tt;
+            float y0, y1;
+            pre_text_row(xt[q][0], xt[q][1], pp.p[0], pp.key, rstep, r, ln64, y0, y1);
+            if (wr) { float* out = pp.cube + (((long)b * il + tt) * 3 + 0) * D; out[ln64] = y0; out[ln64 + 64] = y1; }
+            Xm[tt * XP + ln64] = to_f16_sat(y0); Xm[tt * XP + ln64 + 64] = to_f16_sat(y1);
+            at0 += y0; at1 += y1;
+          }
+        }
+      }
+      ln_rows(0);
+      if (T > 32) { ln_load(8); ln_rows(8); }
+      // rows t >= T of the tile are zero (and of the fp32 cube, where the backward pass reads il rows)
+      {
+        const int c8n = C / 8, nz = (64 - T) * c8n;
+        f16x8 z8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) z8[j] = to_f16(0.f);
+        for (int c = tid; c < nz; c += NT) { const int l = T + c / c8n, c8 = (c - (c / c8n) * c8n) * 8; *reinterpret_cast<f16x8*>(Xm + l * XP + c8) = z8; }
+        if (wr) {
+          float* zc = pp.cube + ((long)b * il + T) * C;
+          for (int c = tid; c < (il - T) * (C / 4); c += NT) *reinterpret_cast<float4*>(zc + 4 * c) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+      // time-phase sums -> LDS [slot][phase][128] (group 0's LayerNorm staging tile: first written behind the second barrier of phase L)
+      float* fpart = reinterpret_cast<float*>(smem + cv.ctl);
+      if (!audio) { fpart[(0 * 4 + ph) * D + ln64] = at0; fpart[(0 * 4 + ph) * D + ln64 + 64] = at1; }
+      fpart[(slot * 4 + ph) * D + ln64] = al0; fpart[(slot * 4 + ph) * D + ln64 + 64] = al1;
+    } else {
     const float* xb = a.x + (long)b * il * C;
     const int nq = C / 4, total = 64 * nq;
     constexpr int NQ = SAVE ? 6 : 12;   // (SAVE build: two passes -- twelve pieces in flight beside both weight request sets spill five registers)                                            // 16-byte pieces per thread and pass: K = 3 (C = 384), two wave groups: ONE pass
@@ -208,6 +299,7 @@ __global__ __launch_bounds__(256 * G) void cube_fwd_fused_kernel(CubeFusedArgs a
         }
       }
     }
+    }
     CPHASE(14);
     // small per-row / per-column parameters -> LDS once (they sit on the critical path of every epilogue otherwise)
     if (tid < 64) { prm[0 * 64 + tid] = pr[0]; prm[1 * 64 + tid] = pr[1]; prm[2 * 64 + tid] = pr[2]; prm[3 * 64 + tid] = pr[3]; }
@@ -218,6 +310,12 @@ __global__ __launch_bounds__(256 * G) void cube_fwd_fused_kernel(CubeFusedArgs a
   }
   __syncthreads();
   CPHASE(1);
+  if constexpr (PRE) {   // temporal means T_F / A_F / V_F of exactly the tile's fp32 values
+    if (tid < 3 * D) {
+      const float* fp = reinterpret_cast<const float*>(smem + cv.ctl) + (tid >> 7) * 4 * D + (tid & 127);
+      a.pre.feats[((long)(tid >> 7) * a.B + b) * D + (tid & 127)] = pre_mean(fp[0], fp[D], fp[2 * D], fp[3 * D], a.pre.T);
+    }
+  }
   if (a.dbg_phase == 1) return;
 
   // ------------------------------------------------------------------ phase L: 64-column slabs, one per wave group and round
@@ -509,6 +607,7 @@ __global__ __launch_bounds__(256 * G) void cube_fwd_fused_kernel(CubeFusedArgs a
           z.z = (yv[4 * j + 2] - mu) * rs * dgam[c + 2] + dbet[c + 2];
           z.w = (yv[4 * j + 3] - mu) * rs * dgam[c + 3] + dbet[c + 3];
           *reinterpret_cast<float4*>(a.d_z + o + 4 * j) = z;
+          if constexpr (HEAD) *reinterpret_cast<float4*>(&CtD[m * CTD + c]) = z;   // (this thread's own positions of the tile: read above)
           if (SAVE) *reinterpret_cast<float4*>(a.d_y + o + 4 * j) = make_float4(yv[4 * j], yv[4 * j + 1], yv[4 * j + 2], yv[4 * j + 3]);
         }
         if (SAVE && part == 0) { a.d_mean[(long)b * R + row] = mu; a.d_rstd[(long)b * R + row] = rs; }
@@ -516,8 +615,23 @@ __global__ __launch_bounds__(256 * G) void cube_fwd_fused_kernel(CubeFusedArgs a
     }
     __syncthreads();
   }
+  if constexpr (HEAD) {
+    // head_fwd_kernel's reduction over the R rows of z this workgroup has just written (its 512-thread shape, its order: cube_bookends.h);
+    // the phase sums go through the weight-image buffers, dead behind the last product
+    float (*hph)[128] = reinterpret_cast<float (*)[128]>(smem + cv.bw);
+    float* hred = reinterpret_cast<float*>(smem + cv.bw) + 4 * 128;
+    hph[tid >> 7][tid & 127] = head_phase_sum(CtD + (tid & 127), CTD, tid >> 7, R);
+    __syncthreads();
+    head_finish(hph, a.head.w, a.head.bias, a.head.ff + (long)b * D, a.head.pred + b, a.head.scale, hred);
+  }
   CPHASE(7);
 }
+
+template <bool SAVE, int NMT, int G>
+__global__ __launch_bounds__(256 * G) void cube_fwd_fused_kernel(CubeFusedArgs a) { cube_fwd_fused_body<SAVE, NMT, G, false, false>(a); }
+// the same block with the tail's bookends folded in: block 0 of a forward tail (PRE) and / or its last block (HEAD); two wave groups
+template <bool SAVE, int NMT, bool PRE, bool HEAD>
+__global__ __launch_bounds__(512) void cube_fwd_bookends_kernel(CubeFusedArgs a) { cube_fwd_fused_body<SAVE, NMT, 2, PRE, HEAD>(a); }
 
 }  // namespace
 
@@ -547,20 +661,40 @@ int cube_block_fwd_fused(hipStream_t s, const CubeFusedArgs& a) {
   const int G = groups == 1 ? 1 : 2;
   const Carve cv = carve(a.K, nmt, G);
   if (cv.total > 160 * 1024) return set_error(MIMRL_ERR_ARG, "cube_fused: LDS budget exceeded (%d B)", cv.total);
-#define LAUNCH_FUSED(SAVE, NMT, GG)                                                                                \
+  if ((a.pre_on || a.head_on) && G != 2) return set_error(MIMRL_ERR_ARG, "cube_fused: the PRE / HEAD modes need two wave groups");
+  if (a.pre_on && (a.K != 3 || a.pre.T < 1 || a.pre.T > a.il)) return set_error(MIMRL_ERR_ARG, "cube_fused: PRE mode needs K = 3 and 1 <= T <= il (T %d, il %d, K %d)", a.pre.T, a.il, a.K);
+  if (a.head_on && nmt != 1) return set_error(MIMRL_ERR_ARG, "cube_fused: HEAD mode needs ol * K <= 64 (got %d)", R);
+#define LAUNCH_KERN(KERN, GG)                                                                                      \
   do {                                                                                                             \
-    auto kern = cube_fwd_fused_kernel<SAVE, NMT, GG>;                                                              \
+    auto kern = KERN;                                                                                              \
     HIPX(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, cv.total)); \
     hipLaunchKernelGGL(kern, dim3(a.B), dim3(256 * GG), cv.total, s, a);                                           \
   } while (0)
-#define LAUNCH_NMT(SAVE, GG)                                                                                       \
+#define LAUNCH_PLAIN(SAVE, GG)                                                                                     \
   do {                                                                                                             \
-    if (nmt == 1) LAUNCH_FUSED(SAVE, 1, GG); else if (nmt == 2) LAUNCH_FUSED(SAVE, 2, GG); else LAUNCH_FUSED(SAVE, 3, GG); \
+    if (nmt == 1) LAUNCH_KERN((cube_fwd_fused_kernel<SAVE, 1, GG>), GG);                                           \
+    else if (nmt == 2) LAUNCH_KERN((cube_fwd_fused_kernel<SAVE, 2, GG>), GG);                                      \
+    else LAUNCH_KERN((cube_fwd_fused_kernel<SAVE, 3, GG>), GG);                                                    \
   } while (0)
-  if (a.save) { if (G == 1) LAUNCH_NMT(true, 1); else LAUNCH_NMT(true, 2); }
-  else { if (G == 1) LAUNCH_NMT(false, 1); else LAUNCH_NMT(false, 2); }
-#undef LAUNCH_NMT
-#undef LAUNCH_FUSED
+#define LAUNCH_PRE(SAVE)                                                                                           \
+  do {                                                                                                             \
+    if (nmt == 1) LAUNCH_KERN((cube_fwd_bookends_kernel<SAVE, 1, true, false>), 2);                                \
+    else if (nmt == 2) LAUNCH_KERN((cube_fwd_bookends_kernel<SAVE, 2, true, false>), 2);                           \
+    else LAUNCH_KERN((cube_fwd_bookends_kernel<SAVE, 3, true, false>), 2);                                         \
+  } while (0)
+#define LAUNCH_MODE(SAVE)                                                                                          \
+  do {                                                                                                             \
+    if (G == 1) LAUNCH_PLAIN(SAVE, 1);                                                                             \
+    else if (a.head_on && a.pre_on) LAUNCH_KERN((cube_fwd_bookends_kernel<SAVE, 1, true, true>), 2);               \
+    else if (a.head_on) LAUNCH_KERN((cube_fwd_bookends_kernel<SAVE, 1, false, true>), 2);                          \
+    else if (a.pre_on) LAUNCH_PRE(SAVE);                                                                           \
+    else LAUNCH_PLAIN(SAVE, 2);                                                                                    \
+  } while (0)
+  if (a.save) LAUNCH_MODE(true); else LAUNCH_MODE(false);
+#undef LAUNCH_MODE
+#undef LAUNCH_PRE
+#undef LAUNCH_PLAIN
+#undef LAUNCH_KERN
   LAUNCH_CHECK();
   return MIMRL_OK;
 }

@@ -287,6 +287,10 @@ struct mimrl_handle {
   bool fused_cube_bwd = true;          // bf16 mode: per-axis fused data-gradient chains of CubeMLP (MIMRL_NO_FUSED_CUBE_BWD=1 disables)
   bool fused_mlp = true;               // bf16 mode: estimator MLP stacks as one kernel per direction (MIMRL_NO_FUSED_MLP=1 disables)
   bool fused_cube = true;              // bf16 mode: CubeMLP blocks as one LDS-resident kernel (MIMRL_NO_FUSED_CUBE=1 disables)
+  bool fused_pre_on = true;            // short sequences: the pre-CubeMLP pieces of a forward tail as one pass (MIMRL_NO_FUSED_TAIL_PRE=1: three launches) ...
+  bool cube_bookends = true;           // ... which is block 0's tile load, and the head the last block's epilogue, where those blocks are fused (MIMRL_NO_FUSED_TAIL_PRE=2:
+                                       // tail_pre / head_fwd stay launches around them).  Both read when the handle is created.
+  bool keep_cube0 = false;             // a forward pass without saved activations still writes the fp32 cube0 (mimrl_probe_encoders reads it)
   int fwd_f16 = 1;                     // bf16 mode: the forward products in front of / inside CubeMLP round their operands to FP16, not bf16
                                        // (GemmDesc::f16, cube_fused.hip: main-gradient cosine vs fp32 0.964 -> 0.998); MIMRL_FWD_BF16=1: off
   int next_event(hipEvent_t* e) {
@@ -482,7 +486,8 @@ struct mimrl_handle {
   int wg_helper = -1;                  // side stream for weight-gradient GEMMs of an MLP stack beside the data-gradient chain / the grouped launch (-1: none)
   int dbg_delay(hipStream_t st, int tag);   // critical-path probe (MIMRL_DBG_DELAY_TAG / _US): a spin kernel behind one phase
   int model_forward(bool train, bool save, int knn_stage = 0, int part = 0);   // part: 0 all, 1 prefix, 2 tail
-  int cube_forward(bool train, bool save);
+  int cube_forward(bool train, bool save, const CubePre* pre = nullptr, const CubeHead* head = nullptr);   // pre / head: fold the tail's bookends into block 0 / the last block
+  bool cube_block_fused(int i, bool train) const;   // block i of cube_forward takes the one-kernel path (cube_fused.hip)
   int cube_backward(int cur_in, int* cur_out);
   int wt_images(hipStream_t st, bool bwd_bf16, bool launch, bool* d_fused);
   int model_backward();

@@ -59,6 +59,12 @@ int mimrl_create(const mimrl_cfg* cfg, void* hip_stream, mimrl_handle** out) {
   MX(det_init());
 #endif
   h->fused_cube = knob("MIMRL_NO_FUSED_CUBE") == nullptr;
+  {   // per handle (not a function-local static): two engines with different settings can live in one process
+    const char* v = knob("MIMRL_NO_FUSED_TAIL_PRE");
+    const bool keep_launches = v && v[0] == '2' && v[1] == 0;
+    h->fused_pre_on = v == nullptr || keep_launches;
+    h->cube_bookends = v == nullptr;
+  }
   h->fused_mlp = knob("MIMRL_NO_FUSED_MLP") == nullptr;
   h->knn_pre = true;
   h->fold_unpack_on = knob("MIMRL_NO_FOLD_UNPACK") == nullptr;
@@ -271,7 +277,10 @@ int mimrl_probe_encoders(mimrl_handle* h, float* cube_x, const float* dcube, con
   MX(h->ensure_images());
   h->ev_next = 0;
   h->bf16 = (h->prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
-  MX(h->model_forward(true, dcube != nullptr, 0, 0));
+  h->keep_cube0 = true;                    // (a pass nobody differentiates does not write the fp32 cube otherwise: engine_forward.hip)
+  const int rf = h->model_forward(true, dcube != nullptr, 0, 0);
+  h->keep_cube0 = false;
+  MX(rf);
   HIPX(hipMemcpyAsync(cube_x, h->cube0, sizeof(float) * nin, hipMemcpyDeviceToDevice, h->stream));
   if (!dcube) return MIMRL_OK;
   if (nin > h->gbuf_floats) return set_error(MIMRL_ERR_STATE, "probe: gradient buffer too small");

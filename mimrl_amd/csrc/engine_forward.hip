@@ -225,11 +225,16 @@ int mimrl_handle::model_forward(bool train, bool save, int knn_stage, int part) 
   const int B = cfg.batch, T = cfg.seq_len, L = cfg.time_len, D = cfg.d_common;
   const long BT_ = (long)B * T;
   const float pdrop[3] = {train ? cfg.dropout[0] : 0.f, train ? cfg.dropout[1] : 0.f, train ? cfg.dropout[2] : 0.f};
-  if (part != 1 && T < L && !pre_done) HIPX(hipMemsetAsync(cube0, 0, sizeof(float) * (size_t)B * L * 3 * D, stream));
   // text_post + ln_relu_drop + feat_mean as one launch, one workgroup per (sample, slot): for short sequences, where the three
   // launches are latency (cfg2: -15 us per tail); a workgroup walking T = 1000 rows loses to the row-parallel kernels (cfg5: +60 us)
-  static const bool fused_pre_on = knob("MIMRL_NO_FUSED_TAIL_PRE") == nullptr;   // tuning knob
   const bool fused_pre = fused_pre_on && T <= 128;
+  // ... and where block 0 of CubeMLP is the one-kernel form, that pass is its tile load (CubePre: no launch, no fp32 cube written and read back
+  // unless the backward pass needs it); likewise the head is the last block's epilogue when its rows fit one LDS tile (CubeHead)
+  const int nbl = cfg.n_blocks;
+  const bool fold_pre = cube_bookends && fused_pre && !pre_done && part != 1 && D == 128 && T <= L && cube_block_fused(0, train);
+  const bool fold_head = cube_bookends && part != 1 && cube_block_fused(nbl - 1, train) && cfg.d_outs[nbl - 1][0] * cfg.d_outs[nbl - 1][1] <= 64 &&
+                         cfg.d_outs[nbl - 1][2] == 128;
+  if (part != 1 && T < L && !pre_done && !fold_pre) HIPX(hipMemsetAsync(cube0, 0, sizeof(float) * (size_t)B * L * 3 * D, stream));
   if (part != 2) {
     MX(fork(0, 5));
     // text branch (side 0): W_t projection (Model.py:395) + dropout -> cube slot 0.  Captured BEFORE the encoders although it
@@ -254,7 +259,17 @@ int mimrl_handle::model_forward(bool train, bool save, int knn_stage, int part) 
     MX(text_post_fwd(stream, tx_raw, cube0, B, T, L, 3, D, 0, pdrop[0], key(), 0));
   }
   // text dropout -> cube slot 0; fwd+bwd sum, LN, ReLU, dropout (Model.py:452-461) -> cube slots 1,2; T_F, A_F, V_F (Model.py:466)
-  if (!pre_done) {
+  CubePre cpre;
+  std::memset(&cpre, 0, sizeof cpre);
+  if (fold_pre) {
+    cpre.tx_raw = tx_raw; cpre.T = T; cpre.key = key(); cpre.feats = bufs.feats + (size_t)B * D;
+    for (int m = 0; m < 2; ++m) { cpre.h2[m] = h1[m]; cpre.gamma[m] = P(ln_g[m]); cpre.beta[m] = P(ln_b[m]); }
+    for (int q = 0; q < 3; ++q) cpre.p[q] = pdrop[q];
+    if (save || keep_cube0) {   // (nothing else reads cube0 or the statistics: the backward pass of a saving tail, and mimrl_probe_encoders)
+      cpre.cube = cube0;
+      for (int m = 0; m < 2; ++m) { cpre.mean[m] = ln_mean[m]; cpre.rstd[m] = ln_rstd[m]; }
+    }
+  } else if (!pre_done) {
     LnSide2 sd[2];
     for (int m = 0; m < 2; ++m)
       sd[m] = LnSide2{h1[m], P(ln_g[m]), P(ln_b[m]), ln_mean[m], ln_rstd[m], nullptr, nullptr, nullptr, 1 + m, pdrop[1 + m],
@@ -266,14 +281,18 @@ int mimrl_handle::model_forward(bool train, bool save, int knn_stage, int part) 
       MX(feat_mean_fwd(stream, cube0, bufs.feats + (size_t)B * D, B, T, L, 3, D));
     }
   }
-  { Scope sc(this, MIMRL_PH_CUBE_FWD); MX(cube_forward(train, save)); }
-  MX(dbg_delay(stream, save ? 2 : 13));
   // head (Model.py:489-515)
   const BlockBuf& last = bb[cfg.n_blocks - 1];
   const int ol = cfg.d_outs[cfg.n_blocks - 1][0], ok = cfg.d_outs[cfg.n_blocks - 1][1], od = cfg.d_outs[cfg.n_blocks - 1][2];
   if (od != D) return set_error(MIMRL_ERR_ARG, "last block d_out must equal d_common (features feed 128-wide estimators)");
-  MX(head_fwd(stream, last.d.z, P(cls_w), P(cls_b), bufs.feats, bufs.pred, B, ol, ok, od, cfg.compose_t_sum,
-              cfg.compose_k_sum));
+  CubeHead chead;
+  chead.w = P(cls_w); chead.bias = P(cls_b); chead.ff = bufs.feats; chead.pred = bufs.pred;
+  chead.scale = (cfg.compose_t_sum ? 1.f : 1.f / ol) * (cfg.compose_k_sum ? 1.f : 1.f / ok);   // (head_fwd's)
+  { Scope sc(this, MIMRL_PH_CUBE_FWD); MX(cube_forward(train, save, fold_pre ? &cpre : nullptr, fold_head ? &chead : nullptr)); }
+  MX(dbg_delay(stream, save ? 2 : 13));
+  if (!fold_head)
+    MX(head_fwd(stream, last.d.z, P(cls_w), P(cls_b), bufs.feats, bufs.pred, B, ol, ok, od, cfg.compose_t_sum,
+                cfg.compose_k_sum));
   (void)ff;
   return MIMRL_OK;
 }
@@ -296,7 +315,18 @@ int mimrl_handle::dual_tail_pre() {
   return MIMRL_OK;
 }
 
-int mimrl_handle::cube_forward(bool train, bool save) {
+// whether block i takes the one-kernel path of cube_forward below (the same test, on the same chain of block shapes)
+bool mimrl_handle::cube_block_fused(int i, bool train) const {
+  if (!bf16 || !fused_cube || i < 0 || i >= cfg.n_blocks) return false;
+  int il = cfg.time_len, ik = 3, id = cfg.d_common;
+  for (int j = 0; j < i; ++j) { il = blk[j].ax[0].out; ik = blk[j].ax[1].out; id = blk[j].ax[2].out; }
+  const BlockW& w = blk[i];
+  const float pmlp[3] = {train ? cfg.dropout_mlp[0] : 0.f, train ? cfg.dropout_mlp[1] : 0.f, train ? cfg.dropout_mlp[2] : 0.f};
+  return cube_fused_supported(il, w.ax[0].hid, w.ax[0].out, ik, w.ax[1].hid, w.ax[1].out, id, w.ax[2].hid, w.ax[2].out, cfg.ln_first != 0,
+                              cfg.res_project[i] != 0, cfg.bias != 0, pmlp);
+}
+
+int mimrl_handle::cube_forward(bool train, bool save, const CubePre* pre, const CubeHead* head) {
   const int B = cfg.batch;
   const float* x = cube0;
   int il = cfg.time_len, ik = 3, id = cfg.d_common;
@@ -332,6 +362,8 @@ int mimrl_handle::cube_forward(bool train, bool save) {
       fa.dbg_phase = dbg_env("MIMRL_CUBE_PHASE") ? atoi(dbg_env("MIMRL_CUBE_PHASE")) : 0;
       fa.B = B; fa.il = il; fa.hl = hl; fa.ol = ol; fa.K = ik; fa.act = cfg.activation; fa.save = save ? 1 : 0;
       if (fa.dbg_phase == 100) { fa.save = 0; fa.dbg_phase = 0; }   // timing-only: skip the saved-activation stores
+      if (pre && i == 0) { fa.pre_on = 1; fa.pre = *pre; }
+      if (head && i == cfg.n_blocks - 1) { fa.head_on = 1; fa.head = *head; }
       MX(cube_block_fwd_fused(stream, fa));
       x = b.d.z;
       il = ol; ik = ok; id = od;

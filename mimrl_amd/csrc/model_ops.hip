@@ -4,7 +4,7 @@
 
 #include <cstring>
 
-#include "kmix_device.h"
+#include "cube_bookends.h"
 
 namespace mimrl {
 
@@ -238,8 +238,8 @@ __global__ __launch_bounds__(256) void tail_pre_kernel(TailPre tp, float* __rest
         if (t < T) {
           const long r = (long)b * T + t;
           float* out = cube + (((long)b * L + t) * K + 0) * D;
-          const float y0 = x[q][0] * drop_scale_at(tp.p_text, key, rstep, 0u, (uint32_t)(r * D + lane));
-          const float y1 = x[q][1] * drop_scale_at(tp.p_text, key, rstep, 0u, (uint32_t)(r * D + lane + 64));
+          float y0, y1;
+          pre_text_row(x[q][0], x[q][1], tp.p_text, key, rstep, r, lane, y0, y1);
           out[lane] = y0; out[lane + 64] = y1;
           acc0 += y0; acc1 += y1;
         }
@@ -261,14 +261,10 @@ __global__ __launch_bounds__(256) void tail_pre_kernel(TailPre tp, float* __rest
         const int t = t0 + 4 * q;
         if (t < T) {                                            // (wave-uniform)
           const long r = (long)b * T + t;
-          const float mu = wave_sum(v[q][0] + v[q][1]) * (1.f / D);
-          const float c0 = v[q][0] - mu, c1 = v[q][1] - mu;
-          const float rs = rsqrtf(wave_sum(c0 * c0 + c1 * c1) * (1.f / D) + LN_EPS);
+          float mu, rs, y0, y1;
+          pre_ln_row(v[q][0], v[q][1], g0, g1, be0, be1, sd.p, key, rstep, sd.stream, r, lane, mu, rs, y0, y1);
           if (lane == 0) { sd.mean[r] = mu; sd.rstd[r] = rs; }
           float* out = cube + (((long)b * L + t) * K + sd.slot) * D;
-          float y0 = c0 * rs * g0 + be0, y1 = c1 * rs * g1 + be1;
-          y0 = (y0 > 0.f ? y0 : 0.f) * drop_scale_at(sd.p, key, rstep, sd.stream, (uint32_t)(r * D + lane));
-          y1 = (y1 > 0.f ? y1 : 0.f) * drop_scale_at(sd.p, key, rstep, sd.stream, (uint32_t)(r * D + lane + 64));
           out[lane] = y0; out[lane + 64] = y1;
           acc0 += y0; acc1 += y1;
         }
@@ -280,7 +276,7 @@ __global__ __launch_bounds__(256) void tail_pre_kernel(TailPre tp, float* __rest
   __syncthreads();
   if (threadIdx.x < D) {
     const int d = threadIdx.x;
-    feats[((long)slot * B + b) * D + d] = (part[0][d] + part[1][d] + part[2][d] + part[3][d]) / T;
+    feats[((long)slot * B + b) * D + d] = pre_mean(part[0][d], part[1][d], part[2][d], part[3][d], T);
   }
   MPHASE(pb, 3);
 }
@@ -434,19 +430,12 @@ __global__ void head_fwd_kernel(const float* __restrict__ x, const float* __rest
   __shared__ float ph[4][128];
   const int b = blockIdx.x;
   float part = 0.f;
-  if (D == 128 && blockDim.x == 512) {
+  if (D == 128 && blockDim.x == 512) {   // (cube_bookends.h: the HEAD mode of cube_fwd_fused_kernel runs the same two helpers on its LDS tile)
     const int d = threadIdx.x & 127, q = threadIdx.x >> 7, n = L * K;
-    const float* xb = x + (long)b * n * D + d;
-    float s = 0.f;
-#pragma unroll 8
-    for (int i = q; i < n; i += 4) s += xb[(long)i * D];
-    ph[q][d] = s;
+    ph[q][d] = head_phase_sum(x + (long)b * n * D + d, D, q, n);
     __syncthreads();
-    if (q == 0) {
-      s = ((ph[0][d] + ph[1][d]) + (ph[2][d] + ph[3][d])) * scale;
-      ff[(long)b * D + d] = s;
-      part = s * w[d];
-    }
+    head_finish(ph, w, bias, ff + (long)b * D, pred + b, scale, red);
+    return;
   } else {
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
       float s = 0.f;
