@@ -8,6 +8,7 @@
 // those gradients are never applied: they are skipped here with no effect on any parameter.//
 // Round 5: the engine is split over six translation units (it was one file of 3,600 lines):
 //   engine.h              this header: constants, helper types, the handle (struct mimrl_handle: arena pointers, schedule state, stream helpers)
+//   scoped.h              Hold<T>: a handle field takes a value for one scope and gets its old one back on every way out
 //   engine_kernels.hip    the step's own small kernels (begin_stage, task loss, finalize_stage1 / 2, stage_boundary) behind launch wrappers
 //   engine_arena.hip      parameter resolution, workspace arena, weight-image tables
 //   engine_forward.hip    model forward: encoders (GRU / LSTM / conv), forward tail, CubeMLP
@@ -37,6 +38,7 @@
 #include "layout.h"
 #include "comm.h"
 #include "model_ops.h"
+#include "scoped.h"
 
 namespace mimrl {
 
@@ -122,6 +124,8 @@ struct mimrl_handle {
   int bank_rows = 0;
   bool bf16 = false;                   // current GEMM operand mode (switched between forward / backward sections)
   int prec = 0;                        // MIMRL_PREC_* bit mask
+  bool bf16_fwd() const { return (prec & MIMRL_PREC_BF16_GEMM_FWD) != 0; }   // operand mode of the forward sections: what bf16 holds between calls
+  bool bf16_bwd() const { return (prec & MIMRL_PREC_BF16_GEMM_BWD) != 0; }   // ... of the backward sections: a Hold of bf16 around each
 
   // parameter handles
   GruDirW gru[2][2][2];          // [mod a=0,v=1][layer][dir]
@@ -231,6 +235,14 @@ struct mimrl_handle {
     std::swap(bufs.feats, alt.feats); std::swap(bufs.pred, alt.pred);
     for (int i = 0; i < MIMRL_MAX_BLOCKS; ++i) std::swap(bb[i], alt.bb[i]);
   }
+  struct FwdSetSwap {   // the two forward sets trade places until the end of a scope (enter(): from a later point of it on)
+    mimrl_handle* h; bool on = false;
+    explicit FwdSetSwap(mimrl_handle* h_, bool now = true) : h(h_) { if (now) enter(); }
+    ~FwdSetSwap() { if (on) h->swap_fwd_set(); }
+    FwdSetSwap(const FwdSetSwap&) = delete;
+    FwdSetSwap& operator=(const FwdSetSwap&) = delete;
+    void enter() { h->swap_fwd_set(); on = true; }
+  };
   bool prefetch = false;               // mode switch (mimrl_set_stage2_prefetch)
   bool defer_tail = false;             // prefetch mode 2: the stage-2 forward tail is NOT issued beside stage 1 but by
                                        // mimrl_stage2_forward_tail (the caller runs it under the stage-1 gradient all-reduce)
@@ -307,7 +319,7 @@ struct mimrl_handle {
     for (int i = 0; i < n; ++i) MX(G_on(st, ds[i]));      // profiling: one event pair per product
     return MIMRL_OK;
   }
-  unsigned side_mask = ~0u;            // sides that may be used right now; work for a masked-out side goes to `stream`
+  unsigned side_mask = ~0u;            // sides that may be used right now (narrowed inside a Hold); work for a masked-out side goes to `stream`
   bool side_on(int i) const { return multi_stream && ((side_mask >> i) & 1u); }
   hipStream_t S(int i) const { return side_on(i) ? side[i] : stream; }
   // side[lo..hi] wait for everything enqueued on `stream` so far
@@ -407,12 +419,12 @@ struct mimrl_handle {
   // The captured graphs bake the input addresses in, so they are cached PER INPUT SET: the caller may alternate between two
   // sets of (text, audio, video, labels) buffers (mimrl_set_inputs) -- the next batch is uploaded into the idle set while the
   // step runs on the active one, and switching costs no device work.
+  struct CachedGraph { hipGraphExec_t exec = nullptr; int rows = -1; };   // rows: the bank size baked into the kernel arguments
   struct GraphSet {
-    hipGraphExec_t graph[3][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // [..][2], [..][3]: the two halves of a split stage-2 gradient pass
-    int rows[3][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}, {-1, -1, -1, -1}};
-    hipGraphExec_t tail = nullptr; int tail_rows = -1;
-    hipGraphExec_t pipe[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // mimrl_stage1_pipe [look-ahead off / on][forward-set parity * 2 + kNN-set parity]
-    int pipe_rows[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};
+    CachedGraph all[3 * 4 + 1 + 2 * 4];
+    CachedGraph& graph(int stage, int k) { return all[stage * 4 + k]; }   // stage 0: the combined step; k 2 / 3: the two halves of a split stage-2 gradient pass
+    CachedGraph& tail() { return all[12]; }
+    CachedGraph& pipe(int ahead, int parity) { return all[13 + ahead * 4 + parity]; }   // mimrl_stage1_pipe [look-ahead off / on][forward-set parity * 2 + kNN-set parity]
     const void* in[4] = {nullptr, nullptr, nullptr, nullptr};
   } gsets[2];
   int cur_set = 0;
@@ -425,14 +437,14 @@ struct mimrl_handle {
   std::vector<hipGraphExec_t> retired;
   void retire(hipGraphExec_t& ex) { if (ex) { retired.push_back(ex); ex = nullptr; } }
   void drop_graphs(int set = -1) {
-    for (int q = 0; q < 2; ++q) {
-      if (set >= 0 && q != set) continue;
-      for (int s = 0; s <= 2; ++s)
-        for (int k = 0; k < 4; ++k) retire(gsets[q].graph[s][k]);
-      retire(gsets[q].tail);
-      for (int a_ = 0; a_ < 2; ++a_) for (int b_ = 0; b_ < 4; ++b_) retire(gsets[q].pipe[a_][b_]);
-    }
+    for (int q = 0; q < 2; ++q)
+      if (set < 0 || q == set)
+        for (CachedGraph& c : gsets[q].all) retire(c.exec);
   }
+  // Replay the graph cached in `slot`; captured first from what `body` enqueues on `stream` when the slot is empty or holds another bank size
+  // (engine_step.hip).  postprocess: the MIMRL_GRAPH_DOT dump of the step graph.
+  template <typename Body>
+  int replay_or_capture(CachedGraph& slot, Body&& body, bool postprocess = false);
   float* P(long off) const { return bufs.main_p + off; }
   float* Gm(long off) const { return bufs.main_g + off; }
   float* CP(long off) const { return bufs.crit_p + off; }
@@ -443,7 +455,7 @@ struct mimrl_handle {
   int conv_backward();
   int lstm_encoders_forward(bool save, int knn_stage);
   int lstm_encoders_backward();
-  int rng_add = 0;
+  int rng_add = 0;                     // 1 (inside a Hold): a pass issued ahead of the begin-of-stage it belongs to uses the key that one will set
   RngKey key() const { return RngKey{(uint32_t)cfg.seed, (uint32_t)(cfg.seed >> 32), d_ints, rng_add}; }
   const float* coef1() const { return d_consts; }
   const float* coef2() const { return d_consts + 11; }
@@ -468,14 +480,6 @@ struct mimrl_handle {
   int carve();
 
   int G_(const GemmDesc& d) { return G_on(stream, d); }
-  // (rounds 2-5 had an accuracy-bisection knob here -- MIMRL_FWD_FP32_SITES: single forward sites with fp32 operands in bf16 mode; the rounded-
-  //  operand oracle tests of round 4 replaced that use, the knob was removed in round 6)
-  static constexpr bool fp32_site(int) { return false; }
-  struct PrecGuard {   // run a scope with fp32 GEMM operands
-    mimrl_handle* h; bool saved;
-    PrecGuard(mimrl_handle* h_, bool force_fp32) : h(h_), saved(h_->bf16) { if (force_fp32) h->bf16 = false; }
-    ~PrecGuard() { h->bf16 = saved; }
-  };
   // weight-gradient work parked by cube_backward and issued on the side streams once the data-gradient chain is through
   // (it then overlaps the latency-bound GRU BPTT instead of competing with the chain for CUs and L2)
   struct Deferred { int kind; int side; GemmDesc g; const float* src; long n0, n1, n2, n3; float* dst;
@@ -493,11 +497,6 @@ struct mimrl_handle {
   int model_backward();
   int encoders_backward(float* dcube);
   int gru_layer_backward(int l);
-  struct StreamGuard {   // route every launch of a scope to another stream
-    mimrl_handle* h; hipStream_t saved;
-    StreamGuard(mimrl_handle* h_, hipStream_t st) : h(h_), saved(h_->stream) { h->stream = st; }
-    ~StreamGuard() { h->stream = saved; }
-  };
   int knn_launch(int stage, hipStream_t st);
   // epoch-ordered critic pass with the next batch's forward pass beside the update (engine_step.hip)
   bool pipe_primed = false; int fwd_parity = 0, pipe_set = 0;   // pipe_set: the input set whose batch's features the primary forward set holds

@@ -108,7 +108,7 @@ int mimrl_create(const mimrl_cfg* cfg, void* hip_stream, mimrl_handle** out) {
     if (hipStreamCreateWithFlags(&h->side[i], hipStreamNonBlocking) != hipSuccess) { mimrl_destroy(h); return set_error(MIMRL_ERR_HIP, "hipStreamCreate failed"); }
   gru_probe_setup();
   h->prec = cfg->precision;
-  h->bf16 = (h->prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
+  h->bf16 = h->bf16_fwd();
   std::memset(&h->bufs, 0, sizeof h->bufs);
   int r = build_layout(h->cfg, &h->layout);
   if (r == 0) r = h->resolve();
@@ -245,23 +245,22 @@ int mimrl_probe_cube(mimrl_handle* h, const float* x, float* out, const float* d
   const size_t nout = (size_t)c.batch * c.d_outs[nb - 1][0] * c.d_outs[nb - 1][1] * c.d_outs[nb - 1][2];
   h->ev_next = 0;
   HIPX(hipMemcpyAsync(h->cube0, x, sizeof(float) * nin, hipMemcpyDeviceToDevice, h->stream));
-  h->bf16 = (h->prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
+  h->bf16 = h->bf16_fwd();
   MX(h->cube_forward(false, dout != nullptr));
   HIPX(hipMemcpyAsync(out, h->bb[nb - 1].d.z, sizeof(float) * nout, hipMemcpyDeviceToDevice, h->stream));
   if (!dout) return MIMRL_OK;
   if (nout > h->gbuf_floats) return set_error(MIMRL_ERR_STATE, "probe: gradient buffer too small");
   HIPX(hipMemsetAsync(h->bufs.main_g, 0, sizeof(float) * h->layout.floats[MIMRL_GROUP_MAIN], h->stream));
   HIPX(hipMemcpyAsync(h->gbuf[0], dout, sizeof(float) * nout, hipMemcpyDeviceToDevice, h->stream));
-  h->bf16 = (h->prec & MIMRL_PREC_BF16_GEMM_BWD) != 0;
-  const bool pre = h->wtT_prebuilt;
-  h->wtT_prebuilt = false;                 // (the combined step builds the D-axis weight images beside the encoders; here: in place)
-  h->deferred.clear();
-  int ci = 0;
-  int r = h->cube_backward(0, &ci);
-  if (r == 0) r = h->flush_deferred();
-  h->wtT_prebuilt = pre;
+  int ci = 0, r;
+  {
+    Hold bwd(h->bf16, h->bf16_bwd());
+    Hold in_place(h->wtT_prebuilt, false);   // (the combined step builds the D-axis weight images beside the encoders; here: in place)
+    h->deferred.clear();
+    r = h->cube_backward(0, &ci);
+    if (r == 0) r = h->flush_deferred();
+  }
   h->kmix_pg_on_side3 = false;
-  h->bf16 = (h->prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
   MX(r);
   MX(h->join(0, 5));
   HIPX(hipMemcpyAsync(dx, h->gbuf[ci], sizeof(float) * nin, hipMemcpyDeviceToDevice, h->stream));
@@ -276,11 +275,11 @@ int mimrl_probe_encoders(mimrl_handle* h, float* cube_x, const float* dcube, con
   const size_t nin = (size_t)c.batch * c.time_len * 3 * c.d_common, nf = (size_t)c.batch * c.d_common;
   MX(h->ensure_images());
   h->ev_next = 0;
-  h->bf16 = (h->prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
-  h->keep_cube0 = true;                    // (a pass nobody differentiates does not write the fp32 cube otherwise: engine_forward.hip)
-  const int rf = h->model_forward(true, dcube != nullptr, 0, 0);
-  h->keep_cube0 = false;
-  MX(rf);
+  h->bf16 = h->bf16_fwd();
+  {
+    Hold keep(h->keep_cube0, true);        // (a pass nobody differentiates does not write the fp32 cube otherwise: engine_forward.hip)
+    MX(h->model_forward(true, dcube != nullptr, 0, 0));
+  }
   HIPX(hipMemcpyAsync(cube_x, h->cube0, sizeof(float) * nin, hipMemcpyDeviceToDevice, h->stream));
   if (!dcube) return MIMRL_OK;
   if (nin > h->gbuf_floats) return set_error(MIMRL_ERR_STATE, "probe: gradient buffer too small");
@@ -288,13 +287,11 @@ int mimrl_probe_encoders(mimrl_handle* h, float* cube_x, const float* dcube, con
   HIPX(hipMemcpyAsync(h->gbuf[0], dcube, sizeof(float) * nin, hipMemcpyDeviceToDevice, h->stream));
   if (dmean) HIPX(hipMemcpyAsync(h->dfeat + nf, dmean, sizeof(float) * 3 * nf, hipMemcpyDeviceToDevice, h->stream));
   else HIPX(hipMemsetAsync(h->dfeat, 0, sizeof(float) * 4 * nf, h->stream));
-  h->bf16 = (h->prec & MIMRL_PREC_BF16_GEMM_BWD) != 0;
   h->deferred.clear();
   h->head_gather_on = false; h->ev_dmean = nullptr; h->kmix_pg_on_side3 = false;
-  const int r = h->encoders_backward(h->gbuf[0]);
-  h->bf16 = (h->prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
   h->grads_clean[2] = false;
-  return r;
+  Hold bwd(h->bf16, h->bf16_bwd());
+  return h->encoders_backward(h->gbuf[0]);
 }
 
 int mimrl_probe_mi(mimrl_handle* h, int stage, float* mi, float* scores, float* dtin_out) {
@@ -302,7 +299,7 @@ int mimrl_probe_mi(mimrl_handle* h, int stage, float* mi, float* scores, float* 
   if (!h->bound) return set_error(MIMRL_ERR_STATE, "mimrl_bind must be called first");
   if (stage != 1 && stage != 2) return set_error(MIMRL_ERR_ARG, "stage must be 1 or 2");
   const int B = h->cfg.batch;
-  const bool bf_fwd = (h->prec & MIMRL_PREC_BF16_GEMM_FWD) != 0, bf_bwd = (h->prec & MIMRL_PREC_BF16_GEMM_BWD) != 0;
+  const bool bf_bwd = h->bf16_bwd();
   h->ev_next = 0;
   MX(h->ensure_images());
   h->imgT_ready = false;
@@ -311,11 +308,13 @@ int mimrl_probe_mi(mimrl_handle* h, int stage, float* mi, float* scores, float* 
     h->imgT_ready = true;
   }
   if (stage == 1) HIPX(hipMemsetAsync(h->bufs.crit_g, 0, sizeof(float) * h->layout.floats[MIMRL_GROUP_CRITIC], h->stream));
-  h->bf16 = bf_fwd;
-  int r = h->mi_forward(stage, true);
-  if (r == 0) { h->bf16 = bf_bwd; h->wg_helper = -1; r = h->mi_backward(stage); }
-  h->bf16 = bf_fwd;
-  MX(r);
+  h->bf16 = h->bf16_fwd();
+  MX(h->mi_forward(stage, true));
+  {
+    Hold bwd(h->bf16, bf_bwd);
+    h->wg_helper = -1;
+    MX(h->mi_backward(stage));
+  }
   MX(h->join(0, 5));
   HIPX(hipMemcpyAsync(mi, h->mi_raw, sizeof(float) * 2 * NE_MI, hipMemcpyDeviceToDevice, h->stream));
   if (scores) {
@@ -335,7 +334,7 @@ int mimrl_probe_cmi(mimrl_handle* h, int stage, const float* cmi_in_, float* log
   if (!h->bound) return set_error(MIMRL_ERR_STATE, "mimrl_bind must be called first");
   if (stage != 1 && stage != 2) return set_error(MIMRL_ERR_ARG, "stage must be 1 or 2");
   const int n = h->nprod();
-  const bool bf_fwd = (h->prec & MIMRL_PREC_BF16_GEMM_FWD) != 0, bf_bwd = (h->prec & MIMRL_PREC_BF16_GEMM_BWD) != 0;
+  const bool bf_bwd = h->bf16_bwd();
   h->ev_next = 0;
   MX(h->ensure_images());
   h->imgT_ready = false;
@@ -346,14 +345,15 @@ int mimrl_probe_cmi(mimrl_handle* h, int stage, const float* cmi_in_, float* log
   if (stage == 1) HIPX(hipMemsetAsync(h->bufs.crit_g, 0, sizeof(float) * h->layout.floats[MIMRL_GROUP_CRITIC], h->stream));
   HIPX(hipMemcpyAsync(h->cmi_in, cmi_in_, sizeof(float) * NE_CMI * 2 * n * 384, hipMemcpyDeviceToDevice, h->stream));
   // cmi_forward minus the kNN / assemble part (Model.py:185-219 on a caller-assembled batch) ...
-  h->bf16 = bf_fwd;
+  h->bf16 = h->bf16_fwd();
   const int cdims[5] = {3 * EMB, HID, HID, HID, 2};
-  int r = h->mlp_stack_forward(NE_CMI, 2 * n, 2 * n, h->cmi0, h->cmi_stride, 4, h->cmi_l, cdims, h->cmi_in, h->cc, h->logits);
-  if (r == 0) r = cmi_loss_fwd_bwd(h->stream, h->logits, h->dlogits, h->bce_raw, h->cmi_raw, h->g_bce(stage), h->g_cmi(stage), NE_CMI, n, h->cfg.cmi_hardtanh);
-  // ... and cmi_backward as a step runs it
-  if (r == 0) { h->bf16 = bf_bwd; h->wg_helper = -1; r = h->cmi_backward(stage); }
-  h->bf16 = bf_fwd;
-  MX(r);
+  MX(h->mlp_stack_forward(NE_CMI, 2 * n, 2 * n, h->cmi0, h->cmi_stride, 4, h->cmi_l, cdims, h->cmi_in, h->cc, h->logits));
+  MX(cmi_loss_fwd_bwd(h->stream, h->logits, h->dlogits, h->bce_raw, h->cmi_raw, h->g_bce(stage), h->g_cmi(stage), NE_CMI, n, h->cfg.cmi_hardtanh));
+  {   // ... and cmi_backward as a step runs it
+    Hold bwd(h->bf16, bf_bwd);
+    h->wg_helper = -1;
+    MX(h->cmi_backward(stage));
+  }
   MX(h->join(0, 5));
   HIPX(hipMemcpyAsync(logits_out, h->logits, sizeof(float) * NE_CMI * 2 * n * 2, hipMemcpyDeviceToDevice, h->stream));
   HIPX(hipMemcpyAsync(vals, h->bce_raw, sizeof(float) * NE_CMI, hipMemcpyDeviceToDevice, h->stream));

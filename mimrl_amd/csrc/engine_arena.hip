@@ -200,15 +200,11 @@ int mimrl_handle::carve() {
     for (int m = 0; m < 2; ++m)
       for (int d = 0; d < 2; ++d) MX(take(&sv[l][m][d], (size_t)gru_saved_floats(cfg.batch, cfg.seq_len)));
   {   // the stage-1 side of prefetch mode (its features / prediction never reach the caller's buffers)
-    float *f0 = bufs.feats, *p0 = bufs.pred;
-    swap_fwd_set();
+    FwdSetSwap alt_set(this);   // (the caller's bufs.feats / bufs.pred sit in `alt` meanwhile, and come back with the swap)
     size_t g2 = 0;
-    int r = carve_fwd(&g2);
-    if (r == 0) r = take(&bufs.feats, 4 * B * D);
-    if (r == 0) r = take(&bufs.pred, B);
-    swap_fwd_set();
-    bufs.feats = f0; bufs.pred = p0;
-    MX(r);
+    MX(carve_fwd(&g2));
+    MX(take(&bufs.feats, 4 * B * D));
+    MX(take(&bufs.pred, B));
   }
   {   // chunk sums of the two-tail pre-CubeMLP launch (model_ops.hip: tail_pre2_kernel); one chunk = none needed
     int nchunk = 1, rpc = 0;

@@ -181,7 +181,7 @@ int mimrl_handle::mi_forward(int stage, bool want_grad) {
   const bool sep = cfg.critic_type == MIMRL_CRITIC_SEPARATE;
   static const bool no_fused_mi = knob("MIMRL_NO_FUSED_MI") != nullptr;        // tuning knobs
   static const bool no_nce_tiled = knob("MIMRL_NO_MI_NCE_TILED") != nullptr;
-  const bool fused_mi = sep && !no_fused_mi && (prec & MIMRL_PREC_BF16_GEMM_FWD) && (prec & MIMRL_PREC_BF16_GEMM_BWD) && mi_sep_fused_supported(B);
+  const bool fused_mi = sep && !no_fused_mi && bf16_fwd() && bf16_bwd() && mi_sep_fused_supported(B);
   const bool nce_tiled = fused_mi && !no_nce_tiled && cfg.bound_type == MIMRL_BOUND_INFONCE && !has_baseline();
   {   // tower inputs: x operand -> slot 2e, y operand -> slot 2e+1
     CopyTable t;
@@ -242,7 +242,7 @@ int mimrl_handle::mi_forward(int stage, bool want_grad) {
       fa.pstride = tower_stride; fa.scores = scores; fa.E = NE_MI; fa.B = B;
       // what the backward pass will read: the fused one takes ReLU bitmasks (+ bf16 values for stage 1's weight gradients), 32x / 2x
       // fewer bytes than the fp32 activations the GEMM-chain backward needs; an evaluation saves nothing
-      concat_compact = want_grad && (prec & MIMRL_PREC_BF16_GEMM_BWD) && imgT_ready && concat_bwd_fused_supported(B, HID);
+      concat_compact = want_grad && bf16_bwd() && imgT_ready && concat_bwd_fused_supported(B, HID);
       const size_t half = (size_t)NE_MI * B * B * (HID / 2);      // floats: the bf16 copy fills the lower half of each fp32-sized buffer
       fa.save = !want_grad ? 0 : !concat_compact ? 1 : stage == 1 ? 2 : 3;
       fa.a0 = ca[0]; fa.a1 = ca[1]; fa.a2 = ca[2];
@@ -505,7 +505,8 @@ int mimrl_handle::route_feature_grads() {
 int mimrl_handle::estimators_all(int stage, bool want_grad, bool backward) {
   Range rg(stage == 1 ? "mimrl.estimators.stage1 (Model.py:305-341)" : "mimrl.estimators.stage2 (Model.py:343-386)");
   DetDefer det_defer(stream, &det_ranges);   // (deterministic build, det.h: the stacks' weight / bias gradients are flushed once, at the end of the stage's estimator work)
-  const bool bf_fwd = (prec & MIMRL_PREC_BF16_GEMM_FWD) != 0 && !fp32_site(8), bf_bwd = (prec & MIMRL_PREC_BF16_GEMM_BWD) != 0;
+  const bool bf_bwd = bf16_bwd();
+  bf16 = bf16_fwd();
   static const bool dbg_skip_imgt = dbg_env("MIMRL_DBG_SKIP_IMGT") != nullptr;   // timing experiments only (stale images: wrong gradients)
   bool imgT_pending = false;
   imgT_ready = false;
@@ -534,8 +535,7 @@ int mimrl_handle::estimators_all(int stage, bool want_grad, bool backward) {
   MX(chain(5, 4));                       // the CMI branch needs the kNN indices
   auto cmi_branch = [&]() -> int {
     if (dbg_skip & 1) return MIMRL_OK;
-    StreamGuard g(this, S(5));
-    bf16 = bf_fwd;
+    Hold on_side5(stream, S(5));
     MX(cmi_forward(stage, want_grad));
     if (imgT_pending) {   // side 3 already waits for the stage boundary (fork above); only the launch was held back
       imgT_pending = false;
@@ -545,22 +545,21 @@ int mimrl_handle::estimators_all(int stage, bool want_grad, bool backward) {
     MX(dbg_delay(stream, stage == 1 ? 4 : 14));
     // (no helper side stream for this branch's weight gradients: it runs on side 5, and a fork / join pair hanging off a captured stream
     //  other than the capture's origin sends this HIP runtime's EndCapture into an endless recursion -- tried, core dump)
-    if (backward) { bf16 = bf_bwd; if (imgT_ready && !(skip_imgT_refresh && stage == 1)) MX(chain(5, 3)); MX(cmi_backward(stage)); MX(dbg_delay(stream, stage == 1 ? 6 : 16)); }
+    if (backward) { Hold bwd(bf16, bf_bwd); if (imgT_ready && !(skip_imgT_refresh && stage == 1)) MX(chain(5, 3)); MX(cmi_backward(stage)); MX(dbg_delay(stream, stage == 1 ? 6 : 16)); }
     return MIMRL_OK;
   };
   auto mi_branch = [&]() -> int {
     if (dbg_skip & 2) return MIMRL_OK;
-    bf16 = bf_fwd;
     { Scope sc(this, MIMRL_PH_EST_FWD); MX(mi_forward(stage, want_grad)); }
     MX(dbg_delay(stream, stage == 1 ? 3 : 15));
     if (backward) {
-      bf16 = bf_bwd;
+      Hold bwd(bf16, bf_bwd);
       if (imgT_ready && !(skip_imgT_refresh && stage == 1)) MX(join(3, 3));
       Scope sc(this, MIMRL_PH_EST_BWD);
-      wg_helper = stage == 1 ? 1 : -1;     // the MI branch is the critical one of stage 1 (tools/critical_path.sh)
-      const int r = mi_backward(stage);
-      wg_helper = -1;
-      MX(r);
+      {
+        Hold helper(wg_helper, stage == 1 ? 1 : -1);   // the MI branch is the critical one of stage 1 (tools/critical_path.sh)
+        MX(mi_backward(stage));
+      }
       MX(dbg_delay(stream, stage == 1 ? 5 : 17));
     }
     return MIMRL_OK;
@@ -569,7 +568,6 @@ int mimrl_handle::estimators_all(int stage, bool want_grad, bool backward) {
   // (MI first, or both forward halves in front of either backward half: DESIGN.md section 7)
   MX(cmi_branch());
   MX(mi_branch());
-  bf16 = bf_fwd;
   if (!multi_stream) return MIMRL_OK;
   return join(5, 5);
 }

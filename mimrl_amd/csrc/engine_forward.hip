@@ -17,7 +17,7 @@ int mimrl_handle::encoders_forward(bool save, int knn_stage) {
   if (!ev_lens) MX(seq_lengths2(S(4), xin[0], dmod[0], lens[0], xin[1], dmod[1], lens[1], B, T));
   // 16-bit operands for the layer-1 projection (see h0h): bf16 recurrence + fp16 forward operands + the packed layer-0 launch that also
   // writes the weight images; a site forced to fp32 (MIMRL_FWD_FP32_SITES) or fp16-stored gx keeps the fp32-operand kernel
-  const bool use_h16 = h16_on && l0_packed && bf16 && fwd_f16 && (prec & MIMRL_PREC_BF16_GRU_FWD) && !fp32_site(4) && !fp32_site(2) && h0h[0] && w1h;
+  const bool use_h16 = h16_on && l0_packed && bf16 && fwd_f16 && (prec & MIMRL_PREC_BF16_GRU_FWD) && h0h[0] && w1h;
   // round 5b: with the fp16 copy feeding the layer-1 projection, dW_ih of layer 1 AND the layer-0 BPTT (h_prev), nobody reads the fp32 layer-0
   // outputs of a training pass any more -- the fused-projection forward then does not write them (262 MB per pass at cfg3).  The two flags
   // describe the pass whose activations the backward will read, i.e. they are recorded by SAVING passes only: in the non-shared prefetch mode
@@ -84,8 +84,7 @@ int mimrl_handle::encoders_forward(bool save, int knn_stage) {
           for (int d = 0; d < 2; ++d) { a.wih[m][d] = pk.wh + ((long)m * 2 + d) * G * KP(); a.bih[m][d] = bpack + ((long)m * 2 + d) * G; }
         }
       } else {
-      PrecGuard pg(this, fp32_site(2));
-      MX(G_on(stream, gd));
+        MX(G_on(stream, gd));
       }
     }
     for (int m = 0; m < 2; ++m) {
@@ -110,7 +109,7 @@ int mimrl_handle::encoders_forward(bool save, int knn_stage) {
       }
       // layer 1: the m == 0 launch covers both modalities; layer 0: video beside audio (side 2, or behind the length scan on side 4
       // when the overlap mode has masked side 2 off -- both are joined in front of the recurrence)
-      if ((l == 0 && !l0_packed) || (l == 1 && m == 0)) { PrecGuard pg(this, fp32_site(l == 0 ? 2 : 4)); MX(G_on(m == 0 ? stream : (side_on(2) ? S(2) : S(4)), gd)); }
+      if ((l == 0 && !l0_packed) || (l == 1 && m == 0)) MX(G_on(m == 0 ? stream : (side_on(2) ? S(2) : S(4)), gd));
       for (int d = 0; d < 2; ++d) {
         const GruDirW& g = gru[m][l][d];
         a.seq[m][d] = GruSeq{gx[m][d], P(g.w_hh), P(g.b_hh), l == 0 ? h0[m] : h1[m], save ? sv[l][m][d] : nullptr};
@@ -249,7 +248,7 @@ int mimrl_handle::model_forward(bool train, bool save, int knn_stage, int part) 
       MX(next_event(&ev_lens));
       HIPX(hipEventRecord(ev_lens, S(0)));
     }
-    { PrecGuard pg(this, fp32_site(1)); GemmDesc g = gemm_nt(bufs.text, cfg.d_t, P(w_t), cfg.d_t, tx_raw, D, (int)BT_, D, cfg.d_t); g.f16 = fwd_f16; MX(G_on(S(0), g)); }
+    { GemmDesc g = gemm_nt(bufs.text, cfg.d_t, P(w_t), cfg.d_t, tx_raw, D, (int)BT_, D, cfg.d_t); g.f16 = fwd_f16; MX(G_on(S(0), g)); }
     MX(dbg_delay(S(0), 10));
     if (part == 0 && !fused_pre) MX(text_post_fwd(S(0), tx_raw, cube0, B, T, L, 3, D, 0, pdrop[0], key(), 0));
     MX(encoders_forward(save, knn_stage));

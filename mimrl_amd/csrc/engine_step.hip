@@ -24,88 +24,74 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
     }
     if (!have_banks) return MIMRL_OK;
     if (!skip_zero) HIPX(hipMemsetAsync(bufs.crit_g, 0, sizeof(float) * layout.floats[MIMRL_GROUP_CRITIC], stream));   // epoch-0 rule: zero loss, no update (Customization.py:97-98, Solver.py:201-203)
-    bf16 = (prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
+    bf16 = bf16_fwd();
     hipEvent_t e_begin = nullptr;
     if (prefetch) {
       MX(next_event(&e_begin));
       HIPX(hipEventRecord(e_begin, stream));
-      if (!share) swap_fwd_set();
     }
-    int r1;
-    if (share) {
-      // (1) prefix, once, into the primary set, on the main stream (text projection on side 0, stage 1's kNN sampler on
-      //     side 4).  It has to be the capture's origin stream that forks the sides: a fork / join pair hanging off
-      //     another captured stream sends this HIP runtime's EndCapture into an endless recursion.
-      side_mask = 0x11u;
-      r1 = model_forward(true, true, knn_pre ? 3 : 1, 1);   // knn_pre: BOTH stages' samplers as one set of launches on side 4 (round 4)
-      side_mask = ~0u;
-      MX(r1);
-      if (wtT_prebuilt) {   // combined step: the CubeMLP backward's weight images (main parameters only) on side 0 -- captured BEHIND the
-        bool df[MIMRL_MAX_BLOCKS];   // encoders (nodes start in capture order: in front of them it delayed the input projections by 12 us);
-        MX(fork(0, 0));              // side 0 is joined at the end of stage 2, which is part of the same capture
-        MX(wt_images(S(0), (prec & MIMRL_PREC_BF16_GEMM_BWD) != 0, true, df));
-        wtT_built = true;
+    {
+      FwdSetSwap alt_set(this, prefetch && !share);   // stage 1 works on the alternate set (shared prefix: from its own tail on)
+      if (share) {
+        // (1) prefix, once, into the primary set, on the main stream (text projection on side 0, stage 1's kNN sampler on
+        //     side 4).  It has to be the capture's origin stream that forks the sides: a fork / join pair hanging off
+        //     another captured stream sends this HIP runtime's EndCapture into an endless recursion.
+        {
+          Hold sides(side_mask, 0x11u);
+          MX(model_forward(true, true, knn_pre ? 3 : 1, 1));   // knn_pre: BOTH stages' samplers as one set of launches on side 4 (round 4)
+        }
+        if (wtT_prebuilt) {   // combined step: the CubeMLP backward's weight images (main parameters only) on side 0 -- captured BEHIND the
+          bool df[MIMRL_MAX_BLOCKS];   // encoders (nodes start in capture order: in front of them it delayed the input projections by 12 us);
+          MX(fork(0, 0));              // side 0 is joined at the end of stage 2, which is part of the same capture
+          MX(wt_images(S(0), bf16_bwd(), true, df));
+          wtT_built = true;
+        }
+        // (stage 2's kNN sampler runs beside the prefix too -- the recurrence leaves half the CUs idle; its anchor key is the step counter
+        //  begin_stage(2) will set: knn_launch(3))
+        // (1b) long sequences: the pre-CubeMLP pieces of both tails in one launch (each source row read once)
+        static const bool dual_pre_on = knob("MIMRL_NO_DUAL_TAIL_PRE") == nullptr;   // tuning knob
+        const bool dual_pre = dual_pre_on && !defer_tail && cfg.seq_len > 128 && cfg.d_common == 128 && rng_add == 0;
+        if (dual_pre) MX(dual_tail_pre());
+        Hold pre(pre_done, dual_pre);   // both tails below skip those pieces
+        hipEvent_t e_prefix = nullptr;
+        MX(next_event(&e_prefix));
+        HIPX(hipEventRecord(e_prefix, stream));
+        // (2) stage 2's tail: one sequential branch behind the prefix on pre_stream, into the primary set
+        //     (deferred mode: issued later by mimrl_stage2_forward_tail, under the stage-1 gradient all-reduce)
+        if (!defer_tail) {
+          HIPX(hipStreamWaitEvent(pre_stream, e_prefix, 0));
+          Hold on_pre(stream, pre_stream);
+          Hold seq(multi_stream, false);
+          Hold key(rng_add, 1);                // begin_stage(2) has not run yet: use the dropout key it will produce
+          MX(model_forward(true, true, 0, 2));
+        }
+        // (3) stage 1's tail on the main stream, into the alternate set, reading the primary set's prefix
+        alt_set.enter();
+        Hold tx(tx_raw, alt.tx_raw);
+        Hold h1a(h1[0], alt.h1[0]);
+        Hold h1v(h1[1], alt.h1[1]);
+        Hold seq(multi_stream, false);
+        MX(model_forward(true, false, 0, 2));
+      } else if (prefetch) {
+        // two forward passes now run side by side; with only 4 hardware queues, more branches would just be serialised
+        // behind one another (measured: with 5+ concurrent branches the step falls back to the sequential time, and the
+        // prefetch chain as a separate graph on its own HIP stream is slower too), so stage 1's own forward pass keeps
+        // two sides only
+        Hold sides(side_mask, 0x11u);        // text branch (side 0) + kNN sampler (side 4; knn_pre: stage 2's as well, one set of launches)
+        MX(model_forward(true, false, knn_pre ? 3 : 1));
+      } else {
+        MX(model_forward(true, false, 1));
       }
-      // (stage 2's kNN sampler runs beside the prefix too -- the recurrence leaves half the CUs idle; its anchor key is the step counter
-      //  begin_stage(2) will set: knn_launch(3))
-      // (1b) long sequences: the pre-CubeMLP pieces of both tails in one launch (each source row read once)
-      static const bool dual_pre_on = knob("MIMRL_NO_DUAL_TAIL_PRE") == nullptr;   // tuning knob
-      const bool dual_pre = dual_pre_on && !defer_tail && cfg.seq_len > 128 && cfg.d_common == 128 && rng_add == 0;
-      if (dual_pre) { MX(dual_tail_pre()); pre_done = true; }
-      struct PreDone { bool& f; ~PreDone() { f = false; } } pre_done_guard{pre_done};
-      hipEvent_t e_prefix = nullptr;
-      MX(next_event(&e_prefix));
-      HIPX(hipEventRecord(e_prefix, stream));
-      // (2) stage 2's tail: one sequential branch behind the prefix on pre_stream, into the primary set
-      //     (deferred mode: issued later by mimrl_stage2_forward_tail, under the stage-1 gradient all-reduce)
-      if (!defer_tail) HIPX(hipStreamWaitEvent(pre_stream, e_prefix, 0));
-      if (!defer_tail) {
-        StreamGuard g(this, pre_stream);
-        const bool ms = multi_stream;
-        multi_stream = false; rng_add = 1;     // begin_stage(2) has not run yet: use the dropout key it will produce
-        r1 = model_forward(true, true, 0, 2);
-        multi_stream = ms; rng_add = 0;
-      }
-      MX(r1);
-      // (3) stage 1's tail on the main stream, into the alternate set, reading the primary set's prefix
-      swap_fwd_set();
-      float* own_tx = tx_raw; float* own_h1[2] = {h1[0], h1[1]};
-      tx_raw = alt.tx_raw; h1[0] = alt.h1[0]; h1[1] = alt.h1[1];
-      {
-        const bool ms = multi_stream;
-        multi_stream = false;
-        r1 = model_forward(true, false, 0, 2);
-        multi_stream = ms;
-      }
-      tx_raw = own_tx; h1[0] = own_h1[0]; h1[1] = own_h1[1];
-    } else if (prefetch) {
-      // two forward passes now run side by side; with only 4 hardware queues, more branches would just be serialised
-      // behind one another (measured: with 5+ concurrent branches the step falls back to the sequential time, and the
-      // prefetch chain as a separate graph on its own HIP stream is slower too), so stage 1's own forward pass keeps
-      // two sides only
-      side_mask = 0x11u;                 // text branch (side 0) + kNN sampler (side 4; knn_pre: stage 2's as well, one set of launches)
-      r1 = model_forward(true, false, knn_pre ? 3 : 1);
-      side_mask = ~0u;
-    } else {
-      r1 = model_forward(true, false, 1);
+      MX(estimators_all(1, true, true));
     }
-    if (r1 == 0) r1 = estimators_all(1, true, true);
-    if (prefetch) swap_fwd_set();
-    MX(r1);
     if (prefetch && !share) {
       // the stage-2 forward pass of this batch depends on nothing stage 1 changes: one sequential branch on its own
       // stream, into the primary buffers (stage 1 itself works on the alternate set); captured behind stage 1's own chain
       HIPX(hipStreamWaitEvent(pre_stream, e_begin, 0));
-      const bool ms = multi_stream;
-      const unsigned sm = side_mask;
-      int r;
-      {
-        StreamGuard g(this, pre_stream);
-        multi_stream = false; rng_add = 1;     // begin_stage(2) has not run yet: use the dropout key it will produce
-        r = model_forward(true, true, 0);
-        multi_stream = ms; rng_add = 0; side_mask = sm;
-      }
-      MX(r);
+      Hold on_pre(stream, pre_stream);
+      Hold seq(multi_stream, false);
+      Hold key(rng_add, 1);                    // begin_stage(2) has not run yet: use the dropout key it will produce
+      MX(model_forward(true, true, 0));
     }
     if (!fuse_boundary) {
       launch_finalize_stage1(stream, bufs.scalars, mi_raw, cmi_raw, bce_raw, coef1());
@@ -129,7 +115,7 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
   }
   LAUNCH_CHECK();
   if (!skip_zero) HIPX(hipMemsetAsync(bufs.main_g, 0, sizeof(float) * layout.floats[MIMRL_GROUP_MAIN], stream));
-  bf16 = (prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
+  bf16 = bf16_fwd();
   if (prefetch && have_banks) {   // forward pass (and kNN sampling) already done beside stage 1
     if (!knn_pre) { MX(fork(4, 4)); MX(knn_launch(2, S(4))); MX(dbg_delay(S(4), 18)); }
   } else {
@@ -151,10 +137,8 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
   launch_finalize_stage2(S(0), bufs.scalars, mi_raw, cmi_raw, coef2(),
                      have_banks ? 1 : 0);
   LAUNCH_CHECK();
-  bf16 = (prec & MIMRL_PREC_BF16_GEMM_BWD) != 0;
-  MX(model_backward());
-  bf16 = (prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
-  return MIMRL_OK;
+  Hold bwd(bf16, bf16_bwd());
+  return model_backward();
 }
 
 int mimrl_handle::enqueue_apply(int stage) {
@@ -243,11 +227,11 @@ int mimrl_handle::enqueue_apply(int stage) {
 // (layout.cpp puts those tensors at the tail of the bucket), so [0, late_offset) -- 0.80 M of 1.08 M floats -- is all-reduced on its own
 // stream while the layer-0 BPTT and its weight gradients run; the tail follows on the main stream.  Captured like everything else.
 int mimrl_handle::enqueue_grads2_reduced(bool skip_zero) {
-  const bool ke = keep_events;
-  split_part = 1; fold_unpack = false;
-  int r = enqueue_grads(2, skip_zero);
-  split_part = 0;
-  MX(r);
+  {
+    Hold part(split_part, 1);
+    Hold no_fold(fold_unpack, false);          // (the packed layer-0 pieces must be IN the bucket before it is reduced)
+    MX(enqueue_grads(2, skip_zero));
+  }
   const long n_main = layout.floats[MIMRL_GROUP_MAIN], early = layout.late_offset;
   hipEvent_t e0, e1;
   MX(next_event(&e0)); MX(next_event(&e1));
@@ -258,18 +242,53 @@ int mimrl_handle::enqueue_grads2_reduced(bool skip_zero) {
     MX(comm_allreduce_sum(comm, bufs.main_g, (size_t)early, comm_s));
     HIPX(hipEventRecord(e1, comm_s));
   }
-  keep_events = true;                       // (the events above stay reserved while part 1 draws its own)
-  bf16 = (prec & MIMRL_PREC_BF16_GEMM_BWD) != 0;
-  r = gru_layer_backward(0);
-  if (r == 0) r = join(0, 5);
-  bf16 = (prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
-  keep_events = ke;
-  MX(r);
+  {
+    Hold reserved(keep_events, true);          // (the events above stay reserved while part 1 draws its own)
+    Hold bwd(bf16, bf16_bwd());
+    MX(gru_layer_backward(0));
+    MX(join(0, 5));
+  }
   if (n_main > early) {
     Range rg("mimrl.stage2.allreduce(main_g[layer-0 tail]) [RCCL]");
     MX(comm_allreduce_sum(comm, bufs.main_g + early, (size_t)(n_main - early), stream));
   }
   if (early > 0) HIPX(hipStreamWaitEvent(stream, e1, 0));
+  return MIMRL_OK;
+}
+
+// Captured-graph diagnostics: MIMRL_GRAPH_DOT=<file> dumps the captured two-stage step (hipGraphDebugDotPrint: kernel names, edges).
+// (Rounds 4-5 also re-inserted fork edges here -- by height, captured-stream-first, pad nodes, a searched permutation: the captured order
+// was a local optimum of all of them, DESIGN.md section 7; the machinery was removed in round 6, git keeps it.)
+static int graph_postprocess(hipGraph_t g) {
+  static const char* dot = knob("MIMRL_GRAPH_DOT");
+  if (dot) HIPX(hipGraphDebugDotPrint(g, dot, hipGraphDebugDotFlagsVerbose));
+  return MIMRL_OK;
+}
+
+// One cached graph: replayed; captured first when the slot is empty or was captured with another bank size.  Capture is illegal on the legacy
+// default stream, so the body's launches go to cap_stream while it runs.
+template <typename Body>
+int mimrl_handle::replay_or_capture(CachedGraph& slot, Body&& body, bool postprocess) {
+  if (slot.exec && slot.rows != bank_rows) retire(slot.exec);   // bank size is baked into the kernel arguments
+  if (!slot.exec) {
+    hipGraph_t g = nullptr;
+    if (!cap_stream) HIPX(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
+    HIPX(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
+    int r;
+    {
+      Hold capturing(stream, cap_stream);    // (put back: user_stream -- `stream` is the caller's outside a capture, and captures do not nest)
+      r = body();
+    }
+    const hipError_t ce = hipStreamEndCapture(cap_stream, &g);
+    if (r != 0) { if (g) (void)hipGraphDestroy(g); return r; }
+    if (ce != hipSuccess) return set_error(MIMRL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
+    if (postprocess) { const int pr = graph_postprocess(g); if (pr != 0) { (void)hipGraphDestroy(g); return pr; } }
+    const hipError_t ie = hipGraphInstantiate(&slot.exec, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (ie != hipSuccess) { slot.exec = nullptr; return set_error(MIMRL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie)); }
+    slot.rows = bank_rows;
+  }
+  HIPX(hipGraphLaunch(slot.exec, stream));
   return MIMRL_OK;
 }
 
@@ -302,23 +321,22 @@ int mimrl_handle::run(int stage, int kind) {
   auto body = [&]() -> int {
     if (kind == 4) {                 // second half of a split stage-2 gradient pass: the layer-0 GRU backward
       if (!keep_events) ev_next = 0;
-      bf16 = (prec & MIMRL_PREC_BF16_GEMM_BWD) != 0;
-      int r = gru_layer_backward(0);
-      if (r == 0) r = join(0, 5);
-      bf16 = (prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
-      return r;
+      Hold bwd(bf16, bf16_bwd());
+      MX(gru_layer_backward(0));
+      return join(0, 5);
     }
     if (kind == 0 && comm && !(stage == 1 && bank_rows <= 0)) {   // data parallel: gradient pass, all-reduce, update -- one enqueue
       if (stage == 2 && comm_split && cfg.encoder == MIMRL_ENCODER_GRU) MX(enqueue_grads2_reduced(skip_zero));
       else { MX(enqueue_grads(stage, skip_zero)); MX(reduce_bucket(stage)); }
       return enqueue_apply(stage);
     }
-    split_part = kind == 3 ? 1 : 0;
-    fold_unpack = kind == 0 && stage == 2 && fold_unpack_on;   // the update follows in the same enqueue: it scatters the packed layer-0 pieces
-    const int r = enqueue_grads(stage, skip_zero);
-    split_part = 0; fold_unpack = false;
-    if (r != 0) unpack_pending = false;
-    MX(r);
+    {
+      Hold part(split_part, kind == 3 ? 1 : 0);
+      Hold fold(fold_unpack, kind == 0 && stage == 2 && fold_unpack_on);   // the update follows in the same enqueue: it scatters the packed layer-0 pieces
+      const int r = enqueue_grads(stage, skip_zero);
+      if (r != 0) unpack_pending = false;
+      MX(r);
+    }
     if (kind == 0) MX(enqueue_apply(stage));
     return MIMRL_OK;
   };
@@ -329,24 +347,7 @@ int mimrl_handle::run(int stage, int kind) {
   if (kind == 1 || kind == 3) grads_clean[stage] = false;
   if (!cfg.use_graph || prof_on) { const int r = body(); part0_done = r == 0 && kind == 3; return r; }
   const int gk = kind >= 3 ? kind - 1 : kind;     // graph cache slot: 0 step, 1 grads, 2 / 3 the halves of a split stage-2 pass
-  hipGraphExec_t& ex = GS().graph[stage][gk];
-  if (ex && GS().rows[stage][gk] != bank_rows) retire(ex);   // bank size is baked into the kernel arguments
-  if (!ex) {
-    hipGraph_t g = nullptr;
-    if (!cap_stream) HIPX(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
-    HIPX(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
-    stream = cap_stream;
-    const int r = body();
-    stream = user_stream;
-    const hipError_t ce = hipStreamEndCapture(cap_stream, &g);
-    if (r != 0) { if (g) (void)hipGraphDestroy(g); return r; }
-    if (ce != hipSuccess) return set_error(MIMRL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-    const hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (ie != hipSuccess) { ex = nullptr; return set_error(MIMRL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie)); }
-    GS().rows[stage][gk] = bank_rows;
-  }
-  HIPX(hipGraphLaunch(ex, stream));
+  MX(replay_or_capture(GS().graph(stage, gk), body));
   part0_done = kind == 3;
   return MIMRL_OK;
 }
@@ -361,23 +362,19 @@ int mimrl_handle::run(int stage, int kind) {
 int mimrl_handle::pipe_forward_body(bool other_inputs) {
   // forward pass (no saved activations: stage 1 trains the critics only) of the bound batch, or of the OTHER input set's batch into the
   // alternate forward set
-  const void* keep_in[3] = {bufs.text, bufs.audio, bufs.video};
-  if (other_inputs) {
-    const GraphSet& o = gsets[1 - cur_set];
-    bufs.text = static_cast<const float*>(o.in[0]); bufs.audio = static_cast<const float*>(o.in[1]); bufs.video = static_cast<const float*>(o.in[2]);
-    swap_fwd_set();
-  }
-  const bool ms = multi_stream;
-  if (other_inputs) multi_stream = false;      // one sequential branch on pre_stream (a fork hanging off a non-origin captured stream breaks EndCapture)
-  rng_add = 1;                                 // the begin-of-stage that belongs to this batch has not run yet
-  bf16 = (prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
-  const int r = model_forward(true, false, 0);
-  rng_add = 0; multi_stream = ms;
-  if (other_inputs) {
-    swap_fwd_set();
-    bufs.text = static_cast<const float*>(keep_in[0]); bufs.audio = static_cast<const float*>(keep_in[1]); bufs.video = static_cast<const float*>(keep_in[2]);
-  }
-  return r;
+  auto pass = [&]() -> int {
+    Hold key(rng_add, 1);                      // the begin-of-stage that belongs to this batch has not run yet
+    bf16 = bf16_fwd();
+    return model_forward(true, false, 0);
+  };
+  if (!other_inputs) return pass();
+  const GraphSet& o = gsets[1 - cur_set];
+  Hold text(bufs.text, static_cast<const float*>(o.in[0]));
+  Hold audio(bufs.audio, static_cast<const float*>(o.in[1]));
+  Hold video(bufs.video, static_cast<const float*>(o.in[2]));
+  FwdSetSwap alt_set(this);
+  Hold seq(multi_stream, false);               // one sequential branch on pre_stream (a fork hanging off a non-origin captured stream breaks EndCapture)
+  return pass();
 }
 
 int mimrl_handle::run_stage1_pipe_prime() {
@@ -387,8 +384,10 @@ int mimrl_handle::run_stage1_pipe_prime() {
   MX(ensure_images());
   if (!keep_events) ev_next = 0;
   if (knn_ovr_mask[0] != 0u) return set_error(MIMRL_ERR_STATE, "mimrl_stage1_pipe_prime: caller-supplied neighbour rows (exact tie order) need the sequential pass");
-  rng_add = 1;                                 // (anchor draws of the call that follows: the key its begin-of-stage will set)
-  { const int rk = knn_launch(1, stream); rng_add = 0; MX(rk); }
+  {
+    Hold key(rng_add, 1);                      // (anchor draws of the call that follows: the key its begin-of-stage will set)
+    MX(knn_launch(1, stream));
+  }
   MX(pipe_forward_body(false));
   pipe_primed = true; pipe_set = cur_set;
   return MIMRL_OK;
@@ -411,7 +410,7 @@ int mimrl_handle::run_stage1_pipe(bool next_valid) {
     if (!keep_events) ev_next = 0;
     launch_begin_stage(stream, d_ints, d_ints + 2, bufs.scalars, 0, 32);
     LAUNCH_CHECK();
-    bf16 = (prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
+    bf16 = bf16_fwd();
     hipEvent_t e_begin = nullptr;
     MX(next_event(&e_begin));
     HIPX(hipEventRecord(e_begin, stream));
@@ -422,16 +421,18 @@ int mimrl_handle::run_stage1_pipe(bool next_valid) {
     // kernels instead of 18 and held the estimators back (gpurun_out/epoch_tl_pipe_stage1.txt of the first two cuts).
     if (next_valid) {
       HIPX(hipStreamWaitEvent(pre_stream, e_begin, 0));
-      StreamGuard g(this, pre_stream);
-      knn_flip ^= 1; rng_add = 1;
-      const int rk = knn_launch(1, stream);
-      knn_flip ^= 1; rng_add = 0;
-      MX(rk);
+      Hold on_pre(stream, pre_stream);
+      {
+        Hold other_set(knn_flip, knn_flip ^ 1);
+        Hold key(rng_add, 1);
+        MX(knn_launch(1, stream));
+      }
       MX(pipe_forward_body(true));
     }
-    const unsigned keep_mask = side_mask;
-    side_mask &= ~(1u << 4);                   // (nothing on side 4 in this call: the CMI branch's chain(5, 4) then orders it behind the main stream)
-    { const int re = estimators_all(1, true, true); side_mask = keep_mask; MX(re); }
+    {
+      Hold sides(side_mask, side_mask & ~(1u << 4));   // (nothing on side 4 in this call: the CMI branch's chain(5, 4) then orders it behind the main stream)
+      MX(estimators_all(1, true, true));
+    }
     launch_finalize_stage1(stream, bufs.scalars, mi_raw, cmi_raw, bce_raw, coef1());
     LAUNCH_CHECK();
     if (next_valid) {                          // rejoin before the stage ends (a captured graph must not leave a dangling branch)
@@ -442,34 +443,10 @@ int mimrl_handle::run_stage1_pipe(bool next_valid) {
     }
     return enqueue_apply(1);
   };
-  int r;
-  if (!cfg.use_graph || prof_on) r = body();
-  else {
-    // (the forward-set roles are baked into the kernel arguments: one graph per parity -- a pass with an even number of batches flips the
-    //  relation between input set and forward set for the next pass; the bank size is baked in as well)
-    hipGraphExec_t& ex = GS().pipe[next_valid ? 1 : 0][fwd_parity * 2 + knn_flip];
-    int& tag = GS().pipe_rows[next_valid ? 1 : 0][fwd_parity * 2 + knn_flip];
-    const int want = bank_rows;
-    if (ex && tag != want) retire(ex);
-    if (!ex) {
-      hipGraph_t g = nullptr;
-      if (!cap_stream) HIPX(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
-      HIPX(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
-      stream = cap_stream;
-      const int rb = body();
-      stream = user_stream;
-      const hipError_t ce = hipStreamEndCapture(cap_stream, &g);
-      if (rb != 0) { if (g) (void)hipGraphDestroy(g); return rb; }
-      if (ce != hipSuccess) return set_error(MIMRL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-      const hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      if (ie != hipSuccess) { ex = nullptr; return set_error(MIMRL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie)); }
-      tag = want;
-    }
-    HIPX(hipGraphLaunch(ex, stream));
-    r = MIMRL_OK;
-  }
-  MX(r);
+  // (the forward-set roles are baked into the kernel arguments: one graph per parity -- a pass with an even number of batches flips the
+  //  relation between input set and forward set for the next pass)
+  if (!cfg.use_graph || prof_on) MX(body());
+  else MX(replay_or_capture(GS().pipe(next_valid ? 1 : 0, fwd_parity * 2 + knn_flip), body));
   if (next_valid) { swap_fwd_set(); fwd_parity ^= 1; knn_flip ^= 1; }   // the look-ahead pass's sets are the current ones of the next call
   else knn_flip = 0;                           // end of the pass: stage 1 / stage 2 back on their own sets
   pipe_primed = next_valid; pipe_set = 1 - cur_set;
@@ -486,41 +463,13 @@ int mimrl_handle::run_fwd2_tail() {
   tail2_needed = false;
   auto body = [&]() -> int {
     if (!keep_events) ev_next = 0;
-    const bool ms = multi_stream;
-    bf16 = (prec & MIMRL_PREC_BF16_GEMM_FWD) != 0;
-    multi_stream = false; rng_add = 1;       // begin_stage(2) has not run yet: use the dropout key it will produce
-    const int r = model_forward(true, true, 0, 2);
-    multi_stream = ms; rng_add = 0;
-    return r;
+    bf16 = bf16_fwd();
+    Hold seq(multi_stream, false);
+    Hold key(rng_add, 1);                    // begin_stage(2) has not run yet: use the dropout key it will produce
+    return model_forward(true, true, 0, 2);
   };
   if (!cfg.use_graph || prof_on) return body();
-  if (GS().tail && GS().tail_rows != bank_rows) retire(GS().tail);
-  if (!GS().tail) {
-    hipGraph_t g = nullptr;
-    if (!cap_stream) HIPX(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
-    HIPX(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
-    stream = cap_stream;
-    const int r = body();
-    stream = user_stream;
-    const hipError_t ce = hipStreamEndCapture(cap_stream, &g);
-    if (r != 0) { if (g) (void)hipGraphDestroy(g); return r; }
-    if (ce != hipSuccess) return set_error(MIMRL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-    const hipError_t ie = hipGraphInstantiate(&GS().tail, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (ie != hipSuccess) { GS().tail = nullptr; return set_error(MIMRL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie)); }
-    GS().tail_rows = bank_rows;
-  }
-  HIPX(hipGraphLaunch(GS().tail, stream));
-  return MIMRL_OK;
-}
-
-// Captured-graph diagnostics: MIMRL_GRAPH_DOT=<file> dumps the captured two-stage step (hipGraphDebugDotPrint: kernel names, edges).
-// (Rounds 4-5 also re-inserted fork edges here -- by height, captured-stream-first, pad nodes, a searched permutation: the captured order
-// was a local optimum of all of them, DESIGN.md section 7; the machinery was removed in round 6, git keeps it.)
-static int graph_postprocess(hipGraph_t g) {
-  static const char* dot = knob("MIMRL_GRAPH_DOT");
-  if (dot) HIPX(hipGraphDebugDotPrint(g, dot, hipGraphDebugDotFlagsVerbose));
-  return MIMRL_OK;
+  return replay_or_capture(GS().tail(), body);
 }
 
 // Solver.step(): stage 1 then stage 2 on the bound batch.  In overlap mode with graphs the two stages are ONE captured
@@ -533,44 +482,31 @@ int mimrl_handle::run_step() {
   const bool combined = cfg.use_graph && !prof_on && prefetch && !defer_tail && bank_rows > 0 && grads_clean[1] && grads_clean[2] && !no_step_graph;
   if (!combined) { MX(run(1, 0)); if (defer_tail) MX(run_fwd2_tail()); return run(2, 0); }
   MX(ensure_images());
-  const bool bf_bwd = (prec & MIMRL_PREC_BF16_GEMM_BWD) != 0;
+  const bool bf_bwd = bf16_bwd();
   const bool use_imgT = bf_bwd && fused_mlp && crit_imgT && ttab.n > 0;
   if (use_imgT && !imgT_valid) {   // the captured stage 1 relies on the images left by the previous step's stage 2
     MX(bf16_transposed_images(user_stream, bufs.crit_p, crit_imgT, ttab));
     imgT_valid = true;
   }
-  hipGraphExec_t& ex = GS().graph[0][0];
-  if (ex && GS().rows[0][0] != bank_rows) retire(ex);   // bank size is baked into the kernel arguments
-  if (!ex) {
-    hipGraph_t g = nullptr;
-    if (!cap_stream) HIPX(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
-    HIPX(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
-    stream = cap_stream;
-    fuse_boundary = true; skip_imgT_refresh = use_imgT; wtT_prebuilt = bf_bwd && fused_cube_bwd;
-    wtT_built = false;
-    int r = enqueue_grads(1, true);
-    if (r == 0) r = reduce_bucket(1);
-    if (r == 0) r = enqueue_apply(1);
-    keep_events = true; fold_unpack = fold_unpack_on && !comm;   // (data parallel: the packed layer-0 pieces must be IN the bucket before it is reduced)
-    if (r == 0) {
-      if (comm && comm_split && cfg.encoder == MIMRL_ENCODER_GRU) r = enqueue_grads2_reduced(true);
-      else { r = enqueue_grads(2, true); if (r == 0) r = reduce_bucket(2); }
+  auto body = [&]() -> int {
+    // capture-only state (engine.h); wtT_built is read only while wtT_prebuilt holds, so what it goes back to is never seen
+    Hold boundary(fuse_boundary, true);
+    Hold images_current(skip_imgT_refresh, use_imgT);
+    Hold prebuilt(wtT_prebuilt, bf_bwd && fused_cube_bwd);
+    Hold built(wtT_built, false);
+    Hold scatter_owed(unpack_pending, false);  // (false between calls; put back on a failure between the stage-2 gradients and their update)
+    MX(enqueue_grads(1, true));
+    MX(reduce_bucket(1));
+    MX(enqueue_apply(1));
+    {
+      Hold reserved(keep_events, true);
+      Hold fold(fold_unpack, fold_unpack_on && !comm);   // (data parallel: the packed layer-0 pieces must be IN the bucket before it is reduced)
+      if (comm && comm_split && cfg.encoder == MIMRL_ENCODER_GRU) MX(enqueue_grads2_reduced(true));
+      else { MX(enqueue_grads(2, true)); MX(reduce_bucket(2)); }
     }
-    keep_events = false; fold_unpack = false;
-    if (r == 0) r = enqueue_apply(2);
-    unpack_pending = false;
-    fuse_boundary = false; skip_imgT_refresh = false; wtT_prebuilt = false;
-    stream = user_stream;
-    const hipError_t ce = hipStreamEndCapture(cap_stream, &g);
-    if (r != 0) { if (g) (void)hipGraphDestroy(g); return r; }
-    if (ce != hipSuccess) return set_error(MIMRL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-    { const int pr = graph_postprocess(g); if (pr != 0) { (void)hipGraphDestroy(g); return pr; } }
-    const hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (ie != hipSuccess) { ex = nullptr; return set_error(MIMRL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie)); }
-    GS().rows[0][0] = bank_rows;
-  }
-  HIPX(hipGraphLaunch(ex, stream));
+    return enqueue_apply(2);
+  };
+  MX(replay_or_capture(GS().graph(0, 0), body, true));
   fwd2_pending = false;
   return MIMRL_OK;
 }
