@@ -28,6 +28,8 @@ extern "C" {
  * 6 x 5 x B^2 x 256 floats (32 GiB at B = 1024, 129 GiB at B = 2048) */
 #define MIMRL_MAX_BATCH 2048
 #define MIMRL_MAX_BATCH_CONCAT 1024
+/* most classes of the classification head (mimrl_cfg.num_class; MOSI / MOSEI use 2 and 7) */
+#define MIMRL_MAX_CLASSES 8
 
 enum { MIMRL_OK = 0, MIMRL_ERR_ARG = -1, MIMRL_ERR_HIP = -2, MIMRL_ERR_STATE = -3, MIMRL_ERR_NODEVICE = -4 };
 enum { MIMRL_GROUP_MAIN = 0, MIMRL_GROUP_CRITIC = 1 };
@@ -43,6 +45,9 @@ enum { MIMRL_BASELINE_CONSTANT = 0, MIMRL_BASELINE_GAUSSAIN = 1, MIMRL_BASELINE_
 enum { MIMRL_ENCODER_GRU = 0, MIMRL_ENCODER_CONV = 1, MIMRL_ENCODER_LSTM = 2 };    /* Model.py:247-257 */
 /* the stage-2 task loss (--loss, Solver.py:172-192): nn.L1Loss, nn.MSELoss, rmse (Utils.py:270), SIMSE (Utils.py:459), ccc_loss (Utils.py:22) */
 enum { MIMRL_TASK_LOSS_MAE = 0, MIMRL_TASK_LOSS_MSE = 1, MIMRL_TASK_LOSS_RMSE = 2, MIMRL_TASK_LOSS_SIMSE = 3, MIMRL_TASK_LOSS_CCC = 4 };
+/* ... and of --task classification (Solver.py:172-178, applied at :324-333): nn.CrossEntropyLoss, FocalLoss (Utils.py:638-649: the focal
+ * factor on the batch-MEAN cross entropy), nn.BCEWithLogitsLoss.  One numbering space with MIMRL_TASK_LOSS_*: a handle has one kind. */
+enum { MIMRL_CLASS_LOSS_CE = 5, MIMRL_CLASS_LOSS_FOCAL = 6, MIMRL_CLASS_LOSS_BCE = 7 };
 
 /* Hot-path subset of Parameters.py:8-70 (same meaning as the flags of the same name). */
 typedef struct mimrl_cfg {
@@ -74,17 +79,21 @@ typedef struct mimrl_cfg {
   int32_t baseline_type;         /* --baseline_type: MIMRL_BASELINE_CONSTANT | _GAUSSAIN | _UNNORMALIZED (VMI.py:72-110; read by tuba / interpolate) */
   int32_t encoder;               /* --encoders: MIMRL_ENCODER_GRU (Model.py:253-255), _CONV (:247-249,437-439) or _LSTM (:250-252) */
   uint64_t seed;                 /* dropout stream seed */
+  int32_t num_class;             /* --num_class: 0 or 1 the one-output head, 2 .. MIMRL_MAX_CLASSES a [num_class, d_common] classifier.  The
+                                    struct grew by this member at its tail under the same ABI number: zero (what every zero-initialising
+                                    caller passes) selects the one-output head */
 } mimrl_cfg;
 
 /* Device pointers (fp32 unless noted).  Flat buckets follow the layout reported by mimrl_layout_entry. */
 typedef struct mimrl_buffers {
   float *main_p, *main_g, *main_m, *main_v;       /* [mimrl_bucket_floats(MAIN)]   */
   float *crit_p, *crit_g, *crit_m, *crit_v;       /* [mimrl_bucket_floats(CRITIC)] */
-  const float *text, *audio, *video, *labels;     /* [B,T,d_t] [B,T,d_a] [B,T,d_v] [B] */
+  const float *text, *audio, *video, *labels;     /* [B,T,d_t] [B,T,d_a] [B,T,d_v] [B] (classification losses: the class index as a float;
+                                                     BCE with one class: 0.0 or 1.0 -- any other value makes the loss NaN) */
   const float *bank_c, *bank_f, *bank_t, *bank_a, *bank_v; /* [cap,1] [cap,128] x4 : previous epoch's stage-2 features */
   int32_t* anchors;                               /* [2][6][B/k] kNN anchor rows for stage 1 / stage 2 (Model.py:81) */
   float *lr_main, *lr_critic;                     /* device scalars (schedulers rewrite them) */
-  float *pred;                                    /* [B] */
+  float *pred;                                    /* [B, num_class] row-major ([B] for the one-output head) */
   float *feats;                                   /* [4][B,128] = F_F, T_F, A_F, V_F */
   float *scalars;                                 /* [MIMRL_NSCALARS] see MIMRL_S_* */
   const int32_t* knn_override;                    /* optional [2][6][(B/k)*k]: neighbour rows for mimrl_set_knn_override_mask */
@@ -213,6 +222,10 @@ int mimrl_set_comm_critic_bf16(mimrl_handle* h, int on);
  * change drops the captured graphs (the kind is fixed when a step is enqueued or captured).  The batch-coupled kinds (RMSE, SIMSE, CCC)
  * are the loss of THIS handle's batch: under data parallelism they are not the loss of the joined batch.  Unknown kind: MIMRL_ERR_ARG. */
 int mimrl_set_task_loss(mimrl_handle* h, int kind);
+/* the same for the classification kinds (MIMRL_CLASS_LOSS_*; a handle created with num_class >= 2 starts with CE, every other with MAE).
+ * MIMRL_ERR_ARG: a kind outside 5..7, CE or Focal with num_class < 2, BCE with num_class > 2; mimrl_set_task_loss in turn refuses a
+ * regression kind on a handle with num_class >= 2.  CE and BCE are means of per-row terms; Focal couples the batch (see above). */
+int mimrl_set_class_loss(mimrl_handle* h, int kind);
 int mimrl_profile_read(mimrl_handle* h, float* ms_sum /*[MIMRL_NPHASES]*/, int32_t* launches /*[MIMRL_NPHASES]*/);  /* syncs; resets */
 /* GEMM family of the eager steps since the last read: out = {algorithmic FLOPs, algorithmic bytes (operands and output once),
  * summed launch durations in ms (HIP events on each launch's own stream), launches}; syncs; resets */
@@ -323,6 +336,10 @@ int mimrl_op_cmi_loss(void* stream, const float* logits, float* dlogits, float* 
 /* task loss `kind` (MIMRL_TASK_LOSS_*) of pred[B] against y[B] into loss[0] and, unless dpred is NULL, dloss/dpred into dpred[B];
  * one workgroup, 1 <= B <= 1024 */
 int mimrl_op_task_loss(void* stream, int kind, const float* pred, const float* y, float* dpred, float* loss, int B);
+/* classification loss `kind` (MIMRL_CLASS_LOSS_*) of logits[B,C] against the class indices y[B] (floats; BCE with C = 1: the targets 0.0 / 1.0)
+ * into loss[0] and, unless dlogits is NULL, dloss/dlogits into dlogits[B,C]; one workgroup, 1 <= B <= 1024, 1 <= C <= MIMRL_MAX_CLASSES;
+ * CE / Focal need C >= 2, BCE C <= 2.  A label that is no integer in [0, C) is never used as an index: the loss comes out NaN. */
+int mimrl_op_class_loss(void* stream, int kind, const float* logits, const float* y, float* dlogits, float* loss, int B, int C);
 /* fused ReLU-MLP stack (critic towers VMI.py:13-22, CMI classifier Model.py:47-72), bf16 MFMA, fp32 in/out.
  * W[l] is [dims[l+1], dims[l]] row-major, group g at + g*pstride (same for b[l], db[l]); activations are
  * [nb, brows, width].  forward: act[l] (l < nl-1) = post-ReLU outputs, out = linear top layer.

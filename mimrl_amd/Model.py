@@ -95,7 +95,7 @@ class Model:
         if labels is not None:
             e.labels.copy_(torch.as_tensor(labels).reshape(-1), non_blocking=True)
         e.forward(train=self.training, with_losses=False)
-        out = e.pred.reshape(-1, 1)
+        out = e.pred.reshape(e.pred.shape[0], -1)      # [B, num_class]
         return [out, e.feats[0], e.feats[1], e.feats[2], e.feats[3]] if return_features else [out]
 
     __call__ = forward
@@ -114,7 +114,7 @@ class Model:
         if predictions is not None:
             pr = torch.as_tensor(predictions)
             if not (pr.is_cuda and pr.data_ptr() == e.pred.data_ptr()):
-                e.pred.copy_(pr.reshape(-1), non_blocking=True)
+                e.pred.copy_(pr.reshape(e.pred.shape), non_blocking=True)
         e.labels.copy_(torch.as_tensor(labels).reshape(-1), non_blocking=True)
         if banks is not None:
             e.set_banks(*banks)

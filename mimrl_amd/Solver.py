@@ -21,7 +21,7 @@ from . import _lib, dist as mdist, synth
 from .Customization import compute_custumized_loss, compute_outputs_from_model, other_model_operations
 from .engine import HipEngine
 from .Model import Model
-from .Utils import TASK_LOSS_FUNCTIONS, log_message, set_logger
+from .Utils import TASK_LOSS_FUNCTIONS, log_message, set_logger, weighted_f1
 
 
 class _Plateau:
@@ -66,7 +66,7 @@ class Solver:
     def __init__(self, opt, loaders=None):
         self.opt = opt
         self.world, self.rank, self.local_rank = mdist.init_from_env()
-        _lib.task_loss_code(opt, self.world)      # --loss: the regression losses; classification and cross-rank batch coupling refused
+        _lib.task_loss_code(opt, self.world)      # --loss against --task / --num_class; cross-rank batch coupling refused
         if opt.optm != "Adam":
             raise NotImplementedError(f"--optm {opt.optm}: only Adam is fused on the MI355X hot path")
         if torch.cuda.is_available():   # BEFORE the loaders: a resident dataset lands on the current device (data.py)
@@ -242,14 +242,14 @@ class Solver:
         return e.scalars[_lib.S1_LOSS]
 
     def stage2_step(self, datas=None, draw_anchors=True):
-        """Model update (Solver.py:221-236).  Returns (loss, mis[8], pred[B,1]) as device tensors."""
+        """Model update (Solver.py:221-236).  Returns (loss, mis[8], pred[B,num_class]) as device tensors."""
         self._prefetch(False)
         e = self._load(datas) if datas is not None else self._engine_for(self._active.cfg.batch)
         if draw_anchors:
             self._anchors(e, 2)
         self._stage(e, 2)
         s = e.scalars
-        return s[_lib.S2_LOSS], s[_lib.S2_MIS:_lib.S2_MIS + 8], e.pred.reshape(-1, 1)
+        return s[_lib.S2_LOSS], s[_lib.S2_MIS:_lib.S2_MIS + 8], e.pred.reshape(e.pred.shape[0], -1)
 
     def step(self, datas):
         """One two-stage iteration on one batch: the unit BASELINE.json's metric counts.  Both stages see the same
@@ -264,7 +264,7 @@ class Solver:
         else:
             e.step()              # mimrl_two_stage_step: both stages as one captured graph
         sc = e.scalars
-        return sc[_lib.S1_LOSS], sc[_lib.S2_LOSS], sc[_lib.S2_MIS:_lib.S2_MIS + 8], e.pred.reshape(-1, 1)
+        return sc[_lib.S1_LOSS], sc[_lib.S2_LOSS], sc[_lib.S2_MIS:_lib.S2_MIS + 8], e.pred.reshape(e.pred.shape[0], -1)
 
     # ------------------------------------------------------------------ Solver.train (Solver.py:194-248)
     def train(self, epoch, train_loader, C_F_all, F_F_all, T_F_all, A_F_all, V_F_all):
@@ -298,7 +298,7 @@ class Solver:
         if self.world > 1:                                                    # banks are replicated
             banks = [mdist.allgather_rows(x, self.world) for x in banks]
         a = acc.cpu().numpy()                                                 # the ONE read-back of the epoch
-        predictions, targets = torch.cat(preds).cpu().numpy().reshape(-1, 1), torch.cat(targs).cpu().numpy().reshape(-1, 1)
+        predictions, targets = torch.cat(preds).cpu().numpy().reshape(-1, self.engine.num_class), torch.cat(targs).cpu().numpy().reshape(-1, 1)
         train_score = self.get_score_from_result(predictions, targets)
         mis = [float(x) / nb for x in a[_lib.S2_MIS:_lib.S2_MIS + 8]]
         return (float(a[_lib.S2_LOSS]) / nb, float(a[_lib.S1_LOSS]) / nb, mis, train_score, *banks)
@@ -320,7 +320,7 @@ class Solver:
                 feats.append([f.cpu() for f in e.feats.clone()])
         a = acc.cpu().numpy()
         nb = len(valid_loader)
-        predictions = torch.cat(preds).cpu().numpy().reshape(-1, 1)
+        predictions = torch.cat(preds).cpu().numpy().reshape(-1, self.engine.num_class)
         targets = torch.cat(targs).cpu().numpy().reshape(-1, 1)
         score = self.get_score_from_result(predictions, targets)
         mis = [float(x) / nb for x in a[_lib.S2_MIS:_lib.S2_MIS + 8]]
@@ -329,20 +329,37 @@ class Solver:
     def compute_loss(self, outputs, labels, stage, C_F_all, F_F_all, T_F_all, A_F_all, V_F_all):
         """Solver.py:317-342 (--loss: Utils.TASK_LOSS_FUNCTIONS) -- losses evaluated on the features of the last forward."""
         predictions = outputs[0]
-        task_loss = TASK_LOSS_FUNCTIONS[self.opt.loss](predictions.reshape(-1),
-                                                       torch.as_tensor(labels, device=predictions.device).reshape(-1))
+        labels_t = torch.as_tensor(labels, device=predictions.device).reshape(-1)
+        loss_fn, C = TASK_LOSS_FUNCTIONS[self.opt.loss], int(getattr(self.opt, "num_class", 1))
+        if self.opt.loss in ("Focal", "CE"):                                                     # Solver.py:324-326
+            task_loss = loss_fn(predictions.reshape(-1, C), labels_t.long())
+        elif self.opt.loss == "BCE" and C == 2:                                                  # Solver.py:327-330
+            task_loss = loss_fn(predictions.reshape(-1, C), torch.nn.functional.one_hot(labels_t.long(), num_classes=C).float())
+        elif self.opt.loss == "BCE":                                                             # Solver.py:331-333
+            task_loss = loss_fn(predictions.reshape(-1), labels_t.float())
+        else:
+            task_loss = loss_fn(predictions.reshape(-1), labels_t)
         return compute_custumized_loss(self.model, task_loss, outputs, labels, None, self.opt, stage, C_F_all, F_F_all,
                                        T_F_all, A_F_all, V_F_all)
 
     # ------------------------------------------------------------------ cold path
     def get_score_from_result(self, predictions, targets):
-        """mae / corr of Utils.calc_metrics (Utils.py:135-136); the class-accuracy metrics are outside the hot path."""
+        """Regression: mae / corr of Utils.calc_metrics (Utils.py:135-136).  Classification (Solver.py:345-356): accuracy and the weighted
+        F1 of the argmax (one class: logit > 0) against the class indices."""
+        if getattr(self.opt, "task", "regression") == "classification":
+            C = int(self.opt.num_class)
+            pred = (predictions.reshape(-1) > 0).astype(np.int64) if C == 1 else predictions.reshape(-1, C).argmax(1)
+            t = np.rint(targets.reshape(-1)).astype(np.int64)
+            return {f"{C}-class_acc": float((pred == t).mean()), f"{C}-f1": weighted_f1(t, pred)}
         p, t = predictions.reshape(-1).astype(np.float64), targets.reshape(-1).astype(np.float64)
         mae = float(np.abs(p - t).mean())
         corr = float(np.corrcoef(p, t)[0, 1]) if p.std() > 0 and t.std() > 0 else 0.0
         return {"mae": mae, "corr": corr}
 
     def current_result_better(self, best, current):
+        if getattr(self.opt, "task", "regression") == "classification":                          # Solver.py:428-429: accuracy, upwards
+            k = f"{int(self.opt.num_class)}-class_acc"
+            return best is None or current[k] > best[k]
         return best is None or current["mae"] < best["mae"]                                      # Solver.py:425-433
 
     # checkpoints: the reference's keys (Solver.py:57-62); 'model' = state_dict with the reference's parameter names,
@@ -454,9 +471,9 @@ class Solver:
             if self.rank == 0:
                 log_message(f"Epoch:[{epoch + 1:3d}] || TrainLoss:[{train_loss:.3f}] TrainMILoss:[{train_loss_mi:.3f}] "
                             f"TrainMI_ft/fa/fv/in/st/sa/sv/cp:[" + "/".join(f"{m:.3f}" for m in train_mis) + "] "
-                            f"Train_mae:[{train_score['mae']:6.3f}] || ValLoss:[{val_loss:.3f}] Val_mae:[{val_score['mae']:6.3f}] "
-                            f"Val_corr:[{val_score['corr']:6.3f}] || TestLoss:[{test_loss:.3f}] Test_mae:[{test_score['mae']:6.3f}] "
-                            f"Test_corr:[{test_score['corr']:6.3f}]")
+                            + " ".join(f"Train_{k}:[{v:6.3f}]" for k, v in list(train_score.items())[:1]) + f" || ValLoss:[{val_loss:.3f}] "
+                            + " ".join(f"Val_{k}:[{v:6.3f}]" for k, v in val_score.items()) + f" || TestLoss:[{test_loss:.3f}] "
+                            + " ".join(f"Test_{k}:[{v:6.3f}]" for k, v in test_score.items()))
         if self.rank == 0:
             log_message("Training complete.")
             for tag, sc in (("Best Valid Score", best_score[0]), ("Test Score at Best Valid", best_score[2]), ("Best Test Score", best_score[1])):

@@ -77,10 +77,42 @@ def ccc_loss(pred: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     return 1.0 - 2.0 * cov / (vy + vp + (my - mp) ** 2 + 1e-10)
 
 
+# --task classification (Solver.py:172-178): logits [B, C] with int64 class indices [B] (CE, Focal), or logits and float targets of one
+# shape (BCE; Solver.compute_loss builds them as Solver.py:327-333 does).
+def ce_loss(logits: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    return torch.nn.functional.cross_entropy(logits, y)
+
+
+def focal_loss(logits: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """Utils.py:638-649 (gamma 2): the focal factor sits on the batch-MEAN cross entropy, not on each row's."""
+    ce = torch.nn.functional.cross_entropy(logits, y)
+    return (1 - torch.exp(-ce)) ** 2 * ce
+
+
+def bce_loss(logits: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    return torch.nn.functional.binary_cross_entropy_with_logits(logits, t)
+
+
 TASK_LOSS_FUNCTIONS = {
     "MAE": lambda p, y: (p - y).abs().mean(),
     "MSE": lambda p, y: ((p - y) ** 2).mean(),
     "RMSE": rmse_loss,
     "SIMSE": simse_loss,
     "CCC": ccc_loss,
+    "CE": ce_loss,
+    "Focal": focal_loss,
+    "BCE": bce_loss,
 }
+
+
+def weighted_f1(targets, predictions) -> float:
+    """F1 per class present in targets or predictions, averaged with the class's share of the targets as weight (what
+    sklearn.metrics.f1_score(average='weighted') computes; a class nobody predicted scores 0).  Solver.py:352."""
+    import numpy as np
+    t, p = np.asarray(targets).reshape(-1), np.asarray(predictions).reshape(-1)
+    total = 0.0
+    for c in np.union1d(t, p):
+        tp = float(np.sum((t == c) & (p == c)))
+        den = float(np.sum(t == c) + np.sum(p == c))
+        total += np.sum(t == c) * (2.0 * tp / den if den > 0 else 0.0)
+    return float(total / len(t)) if len(t) else 0.0

@@ -18,6 +18,7 @@ MAX_BATCH = 2048            # MIMRL_MAX_BATCH: rows per rank
 MAX_BATCH_CONCAT = 1024     # MIMRL_MAX_BATCH_CONCAT: rows per rank with the concat critic
 NCE_WS_FLOATS = 2064        # MIMRL_NCE_WS_FLOATS: workspace of mimrl_op_mi_infonce_rows
 NSCALARS = 64
+MAX_CLASSES = 8             # MIMRL_MAX_CLASSES: outputs of the classification head
 PHASES = ["gemm_misc", "gru_fwd", "gru_bwd", "cube_fwd", "cube_bwd", "est_fwd", "est_bwd", "opt", "model_misc"]
 S1_LOSS, S1_MIS, S1_LOSSES, S2_LOSS, S2_TASK, S2_MIS, S2_LOSSES = 0, 1, 12, 32, 33, 34, 42
 
@@ -49,6 +50,7 @@ class Cfg(C.Structure):
         ("precision", C.c_int32), ("use_graph", C.c_int32), ("device_anchors", C.c_int32), ("baseline_type", C.c_int32),
         ("encoder", C.c_int32),
         ("seed", C.c_uint64),
+        ("num_class", C.c_int32),     # (appended under ABI 6; 0 = the one-output head)
     ]
 
 
@@ -106,6 +108,8 @@ def load() -> C.CDLL:
     lib.mimrl_set_comm_critic_bf16.argtypes = [_FP, C.c_int]
     lib.mimrl_set_task_loss.argtypes = [_FP, C.c_int]
     lib.mimrl_op_task_loss.argtypes = [_FP, C.c_int, _FP, _FP, _FP, _FP, C.c_int]
+    lib.mimrl_set_class_loss.argtypes = [_FP, C.c_int]
+    lib.mimrl_op_class_loss.argtypes = [_FP, C.c_int, _FP, _FP, _FP, _FP, C.c_int, C.c_int]
     lib.mimrl_main_late_offset.argtypes = [_FP]
     lib.mimrl_main_late_offset.restype = C.c_int64
     lib.mimrl_op_gemm16.argtypes = [_FP, _FP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), _FP, _FP, C.c_int,
@@ -172,25 +176,41 @@ EXPORTS = [
     "mimrl_op_gru_saved_floats", "mimrl_op_gru_forward", "mimrl_op_gru_backward", "mimrl_op_gru_wgrad", "mimrl_op_concat_dw", "mimrl_op_mi_bound", "mimrl_op_mi_bound_ex", "mimrl_op_mi_bound_baseline", "mimrl_op_mi_sep_infonce", "mimrl_op_knn",
     "mimrl_op_cmi_loss", "mimrl_op_sample_anchors", "mimrl_knn_r1_host", "mimrl_set_knn_override_mask", "mimrl_op_mlp_stack_forward", "mimrl_op_mlp_stack_backward", "mimrl_op_adam",
     "mimrl_probe_cube", "mimrl_probe_mi", "mimrl_probe_cmi", "mimrl_probe_knn", "mimrl_probe_encoders", "mimrl_set_kernel_stamps", "mimrl_comm_unique_id", "mimrl_set_comm", "mimrl_main_late_offset", "mimrl_set_comm_critic_bf16",
-    "mimrl_stage1_pipe_prime", "mimrl_stage1_pipe", "mimrl_set_task_loss", "mimrl_op_task_loss",
+    "mimrl_stage1_pipe_prime", "mimrl_stage1_pipe", "mimrl_set_task_loss", "mimrl_op_task_loss", "mimrl_set_class_loss", "mimrl_op_class_loss",
     "mimrl_op_mi_infonce_rows", "mimrl_op_lstm_forward", "mimrl_op_lstm_backward", "mimrl_op_recur_btv",
 ]
 
 # --loss (Parameters.py:55, Solver.py:172-192) -> MIMRL_TASK_LOSS_*
 TASK_LOSSES = {"MAE": 0, "MSE": 1, "RMSE": 2, "SIMSE": 3, "CCC": 4}
 BATCH_COUPLED_LOSSES = ("RMSE", "SIMSE", "CCC")
+# ... and under --task classification (Parameters.py:22-23, Solver.py:172-178,324-333) -> MIMRL_CLASS_LOSS_*; one numbering space
+CLASS_LOSSES = {"CE": 5, "Focal": 6, "BCE": 7}
 
 
 def task_loss_code(opt, world: int = 1) -> int:
-    """The engine's task-loss kind for ``opt.loss``.  The classification losses are refused, and so are the batch-coupled regression losses
-    under data parallelism: the reference (nn.DataParallel) evaluates them on the gathered global batch, and a mean of per-rank values is a
-    different loss.  MAE and MSE are means of per-row terms: exact under equal shards, the 1/world being folded into the update."""
+    """The engine's task-loss kind for ``opt.loss`` (``TASK_LOSSES`` or, under ``--task classification``, ``CLASS_LOSSES``).  A loss of
+    one task with the flags of the other is refused, and so are the batch-coupled losses (RMSE, SIMSE, CCC, Focal) under data
+    parallelism: the reference (nn.DataParallel) evaluates them on the gathered global batch, and a mean of per-rank values is a different
+    loss.  MAE, MSE, CE and BCE are means of per-row terms: exact under equal shards, the 1/world being folded into the update."""
     loss = getattr(opt, "loss", "MAE")
-    if loss in ("Focal", "CE", "BCE"):
-        raise NotImplementedError(f"--loss {loss}: classification losses are not on the MI355X path (regression only: "
-                                  f"{', '.join(TASK_LOSSES)})")
+    task = getattr(opt, "task", "regression")
+    ncls = int(getattr(opt, "num_class", 1))
+    if loss in CLASS_LOSSES:
+        if task != "classification":
+            raise NotImplementedError(f"--loss {loss} is a classification loss: it needs --task classification (and --num_class)")
+        if loss == "BCE" and ncls not in (1, 2):
+            raise NotImplementedError(f"--loss BCE needs --num_class 1 or 2, got {ncls} (Solver.py:327-337)")
+        if loss != "BCE" and not 2 <= ncls <= MAX_CLASSES:
+            raise NotImplementedError(f"--loss {loss} needs 2 <= --num_class <= {MAX_CLASSES}, got {ncls}")
+        if int(world) > 1 and loss == "Focal":
+            raise NotImplementedError(f"--loss {loss} couples the whole batch: with {int(world)} ranks each would see only its shard, not the "
+                                      f"reference's global batch; run it on one rank, or use CE / BCE")
+        return CLASS_LOSSES[loss]
     if loss not in TASK_LOSSES:
-        raise NotImplementedError(f"--loss {loss}: unknown task loss (choose one of {', '.join(TASK_LOSSES)})")
+        raise NotImplementedError(f"--loss {loss}: unknown task loss (choose one of {', '.join(list(TASK_LOSSES) + list(CLASS_LOSSES))})")
+    if task == "classification" or ncls > 1:
+        raise NotImplementedError(f"--loss {loss} is a regression loss: --task classification / --num_class {ncls} need one of "
+                                  f"{', '.join(CLASS_LOSSES)}")
     if int(world) > 1 and loss in BATCH_COUPLED_LOSSES:
         raise NotImplementedError(f"--loss {loss} couples the whole batch: with {int(world)} ranks each would see only its shard, not the "
                                   f"reference's global batch; run it on one rank, or use MAE / MSE")
@@ -264,6 +284,7 @@ def make_cfg(opt, d_t: int, d_a: int, d_v: int, seq_len: int = None, bank_capaci
     c.use_graph = int(bool(use_graph))
     c.device_anchors = int(bool(device_anchors))
     c.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    c.num_class = int(getattr(opt, "num_class", 1))
     return c
 
 

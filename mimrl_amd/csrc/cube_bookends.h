@@ -37,19 +37,25 @@ __device__ __forceinline__ float head_phase_sum(const float* xcol, long ld, int 
   for (int i = q; i < n; i += 4) s += xcol[(long)i * ld];
   return s;
 }
-// ... then F_F[d] = ((p0 + p1) + (p2 + p3)) * scale and pred = sum_d F_F[d] * w[d] + bias.  Called by all 512 threads behind the barrier that
-// publishes ph; red: >= 16 floats of LDS.
+// ... then F_F[d] = ((p0 + p1) + (p2 + p3)) * scale and pred[c] = sum_d F_F[d] * w[c * 128 + d] + bias[c] for the C outputs of the head
+// (pred: this sample's row of [B, C]).  Called by all 512 threads behind the barrier that publishes ph; red: >= 16 floats of LDS.  One
+// block_sum per class: class 0 is the one-output head's expression tree and reduction, the further classes follow it.
 __device__ __forceinline__ void head_finish(const float (*ph)[128], const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ ff_row,
-                                            float* __restrict__ pred, float scale, float* red) {
+                                            float* __restrict__ pred, float scale, float* red, int C) {
   const int d = threadIdx.x & 127, q = threadIdx.x >> 7;
-  float part = 0.f;
+  float part = 0.f, s = 0.f;
   if (q == 0) {
-    const float s = ((ph[0][d] + ph[1][d]) + (ph[2][d] + ph[3][d])) * scale;
+    s = ((ph[0][d] + ph[1][d]) + (ph[2][d] + ph[3][d])) * scale;
     ff_row[d] = s;
     part = s * w[d];
   }
   part = block_sum(part, red);
   if (threadIdx.x == 0) *pred = part + bias[0];
+  for (int c = 1; c < C; ++c) {
+    part = q == 0 ? s * w[c * 128 + d] : 0.f;
+    part = block_sum(part, red);
+    if (threadIdx.x == 0) pred[c] = part + bias[c];
+  }
 }
 
 }  // namespace

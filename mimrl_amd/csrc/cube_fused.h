@@ -22,7 +22,7 @@ struct CubePre {
 };
 // HEAD mode (last block, ol * K <= 64): the LayerNorm(D) epilogue keeps its rows in the LDS tile and the workgroup finishes head_fwd_kernel's
 // reduction over them: ff[b, :] and pred[b]
-struct CubeHead { const float *w, *bias; float *ff, *pred; float scale; };
+struct CubeHead { const float *w, *bias; float *ff, *pred; float scale; int C; };   // C: outputs of the head (w [C, 128], pred [B, C])
 
 struct CubeFusedArgs {
   const float* x;                                              // block input  [B, il, K, 128]

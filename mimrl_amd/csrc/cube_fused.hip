@@ -622,7 +622,7 @@ __device__ __forceinline__ void cube_fwd_fused_body(const CubeFusedArgs& a) {
     float* hred = reinterpret_cast<float*>(smem + cv.bw) + 4 * 128;
     hph[tid >> 7][tid & 127] = head_phase_sum(CtD + (tid & 127), CTD, tid >> 7, R);
     __syncthreads();
-    head_finish(hph, a.head.w, a.head.bias, a.head.ff + (long)b * D, a.head.pred + b, a.head.scale, hred);
+    head_finish(hph, a.head.w, a.head.bias, a.head.ff + (long)b * D, a.head.pred + (long)b * a.head.C, a.head.scale, hred, a.head.C);
   }
   CPHASE(7);
 }

@@ -95,7 +95,7 @@ bool det_launch_accumulates(const char* name) {
   if (t_defer) {
     // kernels whose every acc_add target is a gradient-bucket tensor (checked against the sources, round 5b): LayerNorm / bias / weight
     // gradients of the model backward and the estimator stacks, the BPTT's bias gradients, column / row sums into the buckets
-    static const char* const kBucketOnly[] = {"ln_relu_drop_bwd", "head_bwd_kernel", "colln_bwd_kernel", "rowln_bwd_kernel", "kmix_bwd_kernel",
+    static const char* const kBucketOnly[] = {"ln_relu_drop_bwd", "head_bwd_kernel", "head_bwd_cls_kernel", "colln_bwd_kernel", "rowln_bwd_kernel", "kmix_bwd_kernel",
                                               "colsum_kernel", "rowsum_batched", "colln_param_grads", "daxis_param_grads",
                                               "laxis_bwd_kernel", "daxis_bwd_kernel", "gru_bwd_kernel", "top1_bwd_kernel", "concat_dw3_kernel",
                                               "mlp_frag_kernel", "gemm_group_kernel", "gemm_groupk_kernel"};
@@ -105,7 +105,7 @@ bool det_launch_accumulates(const char* name) {
   }
   // kernels that never call acc_add (tests/test_layout.py::test_det_flush_rule_matches_the_sources checks this list against the sources)
   static const char* const kSafe[] = {"_fwd", "adam_kernel", "images_kernel", "bf16_image", "knn_", "sample_anchors", "seq_lengths", "l0_pack", "l0_unpack",
-                                      "text_post", "feat_mean", "tail_pre", "begin_stage", "task_loss_kernel", "finalize_stage", "stage_boundary",
+                                      "text_post", "feat_mean", "tail_pre", "begin_stage", "task_loss_kernel", "class_loss_kernel", "finalize_stage", "stage_boundary",
                                       "cmi_assemble", "copy_rows", "gather_sum4", "wt_transpose", "pad_rows", "mi_bound", "cmi_loss", "pair_expand",
                                       "pair_reduce", "gauss_baseline", "dbg_spin", "det_flush", "dropout_inplace", "add_inplace",
                                       "mi_sep_fused", "gemm_tall_kernel", "concat_ws_reduce"};

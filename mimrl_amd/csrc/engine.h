@@ -62,11 +62,11 @@ static const char* const kVcmi[NE_CMI] = {"ac_t", "ta_c", "vc_t", "tv_c", "tc_a"
 void launch_begin_stage(hipStream_t s, int* rng_step, int* adam_step, float* scalars, int scal_off, int scal_n);
 void launch_bucket_to_bf16(hipStream_t s, const float* src, void* dst, long n);
 void launch_bucket_from_bf16(hipStream_t s, const void* src, float* dst, long n);
-void launch_task_loss(hipStream_t s, int kind, const float* pred, const float* y, float* dpred, float* task, int B);   // kind: MIMRL_TASK_LOSS_*
+void launch_task_loss(hipStream_t s, int kind, const float* pred, const float* y, float* dpred, float* task, int B, int C = 1);   // kind: MIMRL_TASK_LOSS_* (pred [B]) or MIMRL_CLASS_LOSS_* (pred [B, C])
 void launch_finalize_stage1(hipStream_t s, float* scal, const float* mi, const float* cmi, const float* bce, const float* coef1);
 void launch_finalize_stage2(hipStream_t s, float* scal, const float* mi, const float* cmi, const float* coef2, int have_mi);
 void launch_stage_boundary(hipStream_t s, float* scal, const float* mi, const float* cmi, const float* bce, const float* coef1, int* rng_step,
-                           int* adam_step, const float* pred, const float* y, float* dpred, int B, int kind);
+                           int* adam_step, const float* pred, const float* y, float* dpred, int B, int kind, int C = 1);
 
 // roctx ranges (tracing): host-side ranges around the stages and their phases for `rocprofv3 --marker-trace`.  The library
 // is looked up at run time (libroctx64.so ships with ROCm): no link dependency, no cost when it is absent.  Inside a replayed hipGraph a
@@ -257,7 +257,8 @@ struct mimrl_handle {
   // mimrl_set_comm_critic_bf16: the critic bucket (13.4 MB at the benchmark sizes, the larger of the two collectives) crosses the links as
   // bf16 -- rounded once before the all-reduce, summed by RCCL in bf16, widened again in front of clip + Adam
   bool comm_crit_bf16 = false; void* comm_crit16 = nullptr;
-  int task_loss = MIMRL_TASK_LOSS_MAE;   // mimrl_set_task_loss (--loss): every task-loss site of the handle launches this kind
+  int task_loss = MIMRL_TASK_LOSS_MAE;   // mimrl_set_task_loss / mimrl_set_class_loss (--loss): every task-loss site of the handle launches this kind
+  int ncls() const { return cfg.num_class >= 2 ? cfg.num_class : 1; }   // outputs of the head: pred / dpred are [B, ncls()]
   hipStream_t comm_s = nullptr;
   bool comm_split = true;              // MIMRL_DDP_SPLIT=0: the main bucket in one piece behind the whole backward pass
   KernelStamp kstamp;                  // launch stamps of the recurrence kernels (mimrl_set_kernel_stamps); id: 0/1 forward layer 0/1, 2/3 BPTT layer 1/0

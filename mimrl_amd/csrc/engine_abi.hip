@@ -49,6 +49,7 @@ int mimrl_create(const mimrl_cfg* cfg, void* hip_stream, mimrl_handle** out) {
   mimrl_handle* h = new (std::nothrow) mimrl_handle();
   if (!h) return set_error(MIMRL_ERR_STATE, "out of host memory");
   h->cfg = *cfg;
+  if (h->ncls() >= 2) h->task_loss = MIMRL_CLASS_LOSS_CE;   // (a regression loss has no meaning on [B, num_class] logits)
   if (h->cfg.beta1 == 0.f) h->cfg.beta1 = 0.9f;
   if (h->cfg.beta2 == 0.f) h->cfg.beta2 = 0.999f;
   if (h->cfg.adam_eps == 0.f) h->cfg.adam_eps = 1e-8f;
@@ -199,7 +200,7 @@ int mimrl_forward(mimrl_handle* h, int train_mode, int with_losses) {
   MX(h->model_forward(train_mode != 0, false));
   if (!with_losses) return MIMRL_OK;
   launch_task_loss(h->stream, h->task_loss, h->bufs.pred, h->bufs.labels, (float*)nullptr,
-                     h->bufs.scalars + MIMRL_S2_TASK, h->cfg.batch);
+                     h->bufs.scalars + MIMRL_S2_TASK, h->cfg.batch, h->ncls());
   LAUNCH_CHECK();
   h->ev_next = 0;
   if (h->bank_rows > 0) { MX(h->fork(4, 4)); MX(h->knn_launch(2, h->S(4))); MX(h->estimators_all(2, false, false)); }
@@ -224,7 +225,7 @@ int mimrl_estimate(mimrl_handle* h, int stage) {
                        h->bce_raw, h->coef1());
   } else {
     launch_task_loss(h->stream, h->task_loss, h->bufs.pred, h->bufs.labels, (float*)nullptr,
-                       h->bufs.scalars + MIMRL_S2_TASK, h->cfg.batch);
+                       h->bufs.scalars + MIMRL_S2_TASK, h->cfg.batch, h->ncls());
     launch_finalize_stage2(h->stream, h->bufs.scalars, h->mi_raw, h->cmi_raw,
                        h->coef2(), 1);
   }
@@ -483,6 +484,19 @@ int mimrl_set_comm_critic_bf16(mimrl_handle* h, int on) {
 int mimrl_set_task_loss(mimrl_handle* h, int kind) {
   if (!h) return set_error(MIMRL_ERR_ARG, "null handle");
   if (kind < MIMRL_TASK_LOSS_MAE || kind > MIMRL_TASK_LOSS_CCC) return set_error(MIMRL_ERR_ARG, "task loss kind %d unknown", kind);
+  if (h->ncls() >= 2) return set_error(MIMRL_ERR_ARG, "a regression task loss needs the one-output head (num_class %d)", h->cfg.num_class);
+  if (kind == h->task_loss) return MIMRL_OK;
+  HIPX(hipStreamSynchronize(h->user_stream));
+  h->drop_graphs();
+  h->task_loss = kind;
+  return MIMRL_OK;
+}
+
+int mimrl_set_class_loss(mimrl_handle* h, int kind) {
+  if (!h) return set_error(MIMRL_ERR_ARG, "null handle");
+  if (kind < MIMRL_CLASS_LOSS_CE || kind > MIMRL_CLASS_LOSS_BCE) return set_error(MIMRL_ERR_ARG, "classification loss kind %d unknown", kind);
+  if (kind != MIMRL_CLASS_LOSS_BCE && h->ncls() < 2) return set_error(MIMRL_ERR_ARG, "CE / Focal need num_class >= 2 (got %d)", h->cfg.num_class);
+  if (kind == MIMRL_CLASS_LOSS_BCE && h->ncls() > 2) return set_error(MIMRL_ERR_ARG, "BCE needs num_class 1 or 2 (got %d; Solver.py:327-337)", h->cfg.num_class);
   if (kind == h->task_loss) return MIMRL_OK;
   HIPX(hipStreamSynchronize(h->user_stream));
   h->drop_graphs();
@@ -747,6 +761,18 @@ int mimrl_op_task_loss(void* stream, int kind, const float* pred, const float* y
   if (kind < MIMRL_TASK_LOSS_MAE || kind > MIMRL_TASK_LOSS_CCC) return set_error(MIMRL_ERR_ARG, "task loss kind %d unknown", kind);
   if (B < 1 || B > 1024) return set_error(MIMRL_ERR_ARG, "task_loss: batch %d outside [1, 1024]", B);
   launch_task_loss(reinterpret_cast<hipStream_t>(stream), kind, pred, y, dpred, loss, B);
+  LAUNCH_CHECK();
+  return MIMRL_OK;
+}
+
+int mimrl_op_class_loss(void* stream, int kind, const float* logits, const float* y, float* dlogits, float* loss, int B, int C) {
+  if (!logits || !y || !loss) return set_error(MIMRL_ERR_ARG, "class_loss: null argument");
+  if (kind < MIMRL_CLASS_LOSS_CE || kind > MIMRL_CLASS_LOSS_BCE) return set_error(MIMRL_ERR_ARG, "classification loss kind %d unknown", kind);
+  if (B < 1 || B > 1024) return set_error(MIMRL_ERR_ARG, "class_loss: batch %d outside [1, 1024]", B);
+  if (C < 1 || C > MIMRL_MAX_CLASSES) return set_error(MIMRL_ERR_ARG, "class_loss: %d classes outside [1, %d]", C, MIMRL_MAX_CLASSES);
+  if (kind != MIMRL_CLASS_LOSS_BCE && C < 2) return set_error(MIMRL_ERR_ARG, "class_loss: CE / Focal need at least 2 classes");
+  if (kind == MIMRL_CLASS_LOSS_BCE && C > 2) return set_error(MIMRL_ERR_ARG, "class_loss: BCE takes 1 or 2 classes (got %d)", C);
+  launch_task_loss(reinterpret_cast<hipStream_t>(stream), kind, logits, y, dlogits, loss, B, C);
   LAUNCH_CHECK();
   return MIMRL_OK;
 }

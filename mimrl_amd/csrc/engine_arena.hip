@@ -204,7 +204,7 @@ int mimrl_handle::carve() {
     size_t g2 = 0;
     MX(carve_fwd(&g2));
     MX(take(&bufs.feats, 4 * B * D));
-    MX(take(&bufs.pred, B));
+    MX(take(&bufs.pred, B * ncls()));
   }
   {   // chunk sums of the two-tail pre-CubeMLP launch (model_ops.hip: tail_pre2_kernel); one chunk = none needed
     int nchunk = 1, rpc = 0;
@@ -226,7 +226,7 @@ int mimrl_handle::carve() {
     const int hl = cfg.d_hiddens[i][0], ol = cfg.d_outs[i][0];
     if (hl % 4 != 0) MX(take(&w2p[i], (size_t)ol * ((hl + 3) & ~3) + 64));
   }
-  MX(take(&dpred, B));
+  MX(take(&dpred, B * ncls()));
   if (cfg.encoder == MIMRL_ENCODER_GRU) {
     MX(take(&xpack, 2 * BT_ * KP())); MX(take(&wpack, (size_t)4 * G * KP())); MX(take(&bpack, (size_t)4 * G));
     MX(take(&dwih_pack, (size_t)4 * G * KP())); MX(take(&dwhh_pack, (size_t)4 * G * H));

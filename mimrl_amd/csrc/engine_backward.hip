@@ -381,7 +381,7 @@ int mimrl_handle::model_backward() {
   const int ol = cfg.d_outs[nb - 1][0], ok = cfg.d_outs[nb - 1][1], od = cfg.d_outs[nb - 1][2];
   // head backward -> gradient of the last cube output (in gbuf[0])
   MX(head_bwd(stream, dfeat, dpred, P(cls_w), bufs.feats, gbuf[0], Gm(cls_w), Gm(cls_b), B, ol, ok, od,
-              cfg.compose_t_sum, cfg.compose_k_sum, head_gather_on ? &head_gather : nullptr));
+              cfg.compose_t_sum, cfg.compose_k_sum, head_gather_on ? &head_gather : nullptr, ncls()));
   int ci = 0;
   deferred.clear();
   { Scope sc(this, MIMRL_PH_CUBE_BWD); MX(cube_backward(0, &ci)); }

@@ -285,13 +285,13 @@ int mimrl_handle::model_forward(bool train, bool save, int knn_stage, int part) 
   const int ol = cfg.d_outs[cfg.n_blocks - 1][0], ok = cfg.d_outs[cfg.n_blocks - 1][1], od = cfg.d_outs[cfg.n_blocks - 1][2];
   if (od != D) return set_error(MIMRL_ERR_ARG, "last block d_out must equal d_common (features feed 128-wide estimators)");
   CubeHead chead;
-  chead.w = P(cls_w); chead.bias = P(cls_b); chead.ff = bufs.feats; chead.pred = bufs.pred;
+  chead.w = P(cls_w); chead.bias = P(cls_b); chead.ff = bufs.feats; chead.pred = bufs.pred; chead.C = ncls();
   chead.scale = (cfg.compose_t_sum ? 1.f : 1.f / ol) * (cfg.compose_k_sum ? 1.f : 1.f / ok);   // (head_fwd's)
   { Scope sc(this, MIMRL_PH_CUBE_FWD); MX(cube_forward(train, save, fold_pre ? &cpre : nullptr, fold_head ? &chead : nullptr)); }
   MX(dbg_delay(stream, save ? 2 : 13));
   if (!fold_head)
     MX(head_fwd(stream, last.d.z, P(cls_w), P(cls_b), bufs.feats, bufs.pred, B, ol, ok, od, cfg.compose_t_sum,
-                cfg.compose_k_sum));
+                cfg.compose_k_sum, ncls()));
   (void)ff;
   return MIMRL_OK;
 }

@@ -22,6 +22,14 @@ __global__ void task_loss_kernel(const float* __restrict__ pred, const float* __
   task_loss_body<KIND, false>(pred, y, dpred, task, B, red);
 }
 
+// the classification losses (task_loss.h: class_loss_body): logits [B, C], y [B] class indices as floats (dlogits may be null)
+template <int KIND>
+__global__ void class_loss_kernel(const float* __restrict__ logits, const float* __restrict__ y, float* __restrict__ dlogits,
+                                  float* __restrict__ task, int B, int C) {
+  __shared__ float red[16];
+  class_loss_body<KIND, false>(logits, y, dlogits, task, B, C, red);
+}
+
 // Model.py:341 + Customization.py:100-102
 __global__ void finalize_stage1_kernel(float* scal, const float* mi, const float* cmi, const float* bce, const float* coef1) {
   if (threadIdx.x != 0) return;
@@ -103,8 +111,11 @@ void launch_bucket_from_bf16(hipStream_t s, const void* src, float* dst, long n)
 void launch_begin_stage(hipStream_t s, int* rng_step, int* adam_step, float* scalars, int scal_off, int scal_n) {
   hipLaunchKernelGGL(begin_stage_kernel, dim3(1), dim3(64), 0, s, rng_step, adam_step, scalars, scal_off, scal_n);
 }
-void launch_task_loss(hipStream_t s, int kind, const float* pred, const float* y, float* dpred, float* task, int B) {
+void launch_task_loss(hipStream_t s, int kind, const float* pred, const float* y, float* dpred, float* task, int B, int C) {
   switch (kind) {
+    case MIMRL_CLASS_LOSS_CE: hipLaunchKernelGGL(class_loss_kernel<MIMRL_CLASS_LOSS_CE>, dim3(1), dim3(256), 0, s, pred, y, dpred, task, B, C); break;
+    case MIMRL_CLASS_LOSS_FOCAL: hipLaunchKernelGGL(class_loss_kernel<MIMRL_CLASS_LOSS_FOCAL>, dim3(1), dim3(256), 0, s, pred, y, dpred, task, B, C); break;
+    case MIMRL_CLASS_LOSS_BCE: hipLaunchKernelGGL(class_loss_kernel<MIMRL_CLASS_LOSS_BCE>, dim3(1), dim3(256), 0, s, pred, y, dpred, task, B, C); break;
     case MIMRL_TASK_LOSS_MSE: hipLaunchKernelGGL(task_loss_kernel<MIMRL_TASK_LOSS_MSE>, dim3(1), dim3(256), 0, s, pred, y, dpred, task, B); break;
     case MIMRL_TASK_LOSS_RMSE: hipLaunchKernelGGL(task_loss_kernel<MIMRL_TASK_LOSS_RMSE>, dim3(1), dim3(256), 0, s, pred, y, dpred, task, B); break;
     case MIMRL_TASK_LOSS_SIMSE: hipLaunchKernelGGL(task_loss_kernel<MIMRL_TASK_LOSS_SIMSE>, dim3(1), dim3(256), 0, s, pred, y, dpred, task, B); break;
@@ -119,9 +130,12 @@ void launch_finalize_stage2(hipStream_t s, float* scal, const float* mi, const f
   hipLaunchKernelGGL(finalize_stage2_kernel, dim3(1), dim3(64), 0, s, scal, mi, cmi, coef2, have_mi);
 }
 void launch_stage_boundary(hipStream_t s, float* scal, const float* mi, const float* cmi, const float* bce, const float* coef1, int* rng_step,
-                           int* adam_step, const float* pred, const float* y, float* dpred, int B, int kind) {
-  const StageBoundaryArgs a{scal, mi, cmi, bce, coef1, rng_step, adam_step, pred, y, dpred, B};
+                           int* adam_step, const float* pred, const float* y, float* dpred, int B, int kind, int C) {
+  const StageBoundaryArgs a{scal, mi, cmi, bce, coef1, rng_step, adam_step, pred, y, dpred, B, C};
   switch (kind) {
+    case MIMRL_CLASS_LOSS_CE: hipLaunchKernelGGL(stage_boundary_kernel<MIMRL_CLASS_LOSS_CE>, dim3(1), dim3(256), 0, s, a); break;
+    case MIMRL_CLASS_LOSS_FOCAL: hipLaunchKernelGGL(stage_boundary_kernel<MIMRL_CLASS_LOSS_FOCAL>, dim3(1), dim3(256), 0, s, a); break;
+    case MIMRL_CLASS_LOSS_BCE: hipLaunchKernelGGL(stage_boundary_kernel<MIMRL_CLASS_LOSS_BCE>, dim3(1), dim3(256), 0, s, a); break;
     case MIMRL_TASK_LOSS_MSE: hipLaunchKernelGGL(stage_boundary_kernel<MIMRL_TASK_LOSS_MSE>, dim3(1), dim3(256), 0, s, a); break;
     case MIMRL_TASK_LOSS_RMSE: hipLaunchKernelGGL(stage_boundary_kernel<MIMRL_TASK_LOSS_RMSE>, dim3(1), dim3(256), 0, s, a); break;
     case MIMRL_TASK_LOSS_SIMSE: hipLaunchKernelGGL(stage_boundary_kernel<MIMRL_TASK_LOSS_SIMSE>, dim3(1), dim3(256), 0, s, a); break;

@@ -108,7 +108,7 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
   if (fuse_boundary) {
     if (!boundary_in_adam)   // (else: workgroup 0 of the critic Adam launch did it -- enqueue_apply)
       launch_stage_boundary(stream, bufs.scalars, mi_raw, cmi_raw, bce_raw, coef1(), d_ints, d_ints + 1,
-                         bufs.pred, bufs.labels, dpred, B, task_loss);
+                         bufs.pred, bufs.labels, dpred, B, task_loss, ncls());
     boundary_in_adam = false;
   } else {
     launch_begin_stage(stream, d_ints, d_ints + 1, bufs.scalars, 32, 32);
@@ -122,7 +122,7 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
     MX(model_forward(true, true, have_banks ? 2 : 0));
   }
   if (!fuse_boundary) {
-    launch_task_loss(stream, task_loss, bufs.pred, bufs.labels, dpred, bufs.scalars + MIMRL_S2_TASK, B);
+    launch_task_loss(stream, task_loss, bufs.pred, bufs.labels, dpred, bufs.scalars + MIMRL_S2_TASK, B, ncls());
     LAUNCH_CHECK();
   }
   if (have_banks) {
@@ -194,7 +194,7 @@ int mimrl_handle::enqueue_apply(int stage) {
       if (a.frag.n == nfwd) { a.frag.dst = crit_frag; fwd_in_adam = true; } else a.frag.n = 0;
     }
     a.sb_on = 1;
-    a.sb = StageBoundaryArgs{bufs.scalars, mi_raw, cmi_raw, bce_raw, coef1(), d_ints, d_ints + 1, bufs.pred, bufs.labels, dpred, cfg.batch};
+    a.sb = StageBoundaryArgs{bufs.scalars, mi_raw, cmi_raw, bce_raw, coef1(), d_ints, d_ints + 1, bufs.pred, bufs.labels, dpred, cfg.batch, ncls()};
     boundary_in_adam = true;
   }
   MX(adam_step(stream, a, task_loss));

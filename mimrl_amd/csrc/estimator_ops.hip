@@ -975,6 +975,9 @@ int adam_step(hipStream_t s, const AdamArgs& a, int sb_kind) {
     if (a.n % 8 != 0 || a.fold.n != 0 || a.frag.n > 12 || (a.frag.n > 0 && a.n >= (1L << 24))) return set_error(MIMRL_ERR_ARG, "adam_step: the 8-wide kernel needs n %% 8 == 0, no parked pieces, <= 12 image entries");
     const dim3 grid(grid_for(a.n / 8, 256, 2048));
     switch (a.sb_on ? sb_kind : MIMRL_TASK_LOSS_MAE) {
+      case MIMRL_CLASS_LOSS_CE: hipLaunchKernelGGL(adam8_kernel<MIMRL_CLASS_LOSS_CE>, grid, dim3(256), 0, s, a); break;
+      case MIMRL_CLASS_LOSS_FOCAL: hipLaunchKernelGGL(adam8_kernel<MIMRL_CLASS_LOSS_FOCAL>, grid, dim3(256), 0, s, a); break;
+      case MIMRL_CLASS_LOSS_BCE: hipLaunchKernelGGL(adam8_kernel<MIMRL_CLASS_LOSS_BCE>, grid, dim3(256), 0, s, a); break;
       case MIMRL_TASK_LOSS_MSE: hipLaunchKernelGGL(adam8_kernel<MIMRL_TASK_LOSS_MSE>, grid, dim3(256), 0, s, a); break;
       case MIMRL_TASK_LOSS_RMSE: hipLaunchKernelGGL(adam8_kernel<MIMRL_TASK_LOSS_RMSE>, grid, dim3(256), 0, s, a); break;
       case MIMRL_TASK_LOSS_SIMSE: hipLaunchKernelGGL(adam8_kernel<MIMRL_TASK_LOSS_SIMSE>, grid, dim3(256), 0, s, a); break;

@@ -12,6 +12,8 @@ static const char* kVcmi[6] = {"ac_t", "ta_c", "vc_t", "tv_c", "tc_a", "tc_v"};
 
 int validate_cfg(const mimrl_cfg& c) {
   if (c.batch < 1) return set_error(MIMRL_ERR_ARG, "batch must be >= 1");
+  if (c.num_class < 0 || c.num_class > MIMRL_MAX_CLASSES)
+    return set_error(MIMRL_ERR_ARG, "num_class %d outside [0, MIMRL_MAX_CLASSES = %d]", c.num_class, MIMRL_MAX_CLASSES);
   if (c.d_common != 128)
     return set_error(MIMRL_ERR_ARG, "d_common must be 128 (the reference hard-codes embed_dim=128, Model.py:285; got %d)",
                      c.d_common);
@@ -102,8 +104,9 @@ int build_layout(const mimrl_cfg& c, Layout* out) {
       for (int ax = 0; ax < 3; ++ax) add(pre + ".res_projection_" + ax_name[ax] + ".weight", c.d_outs[i][ax], din[ax]);
     for (int ax = 0; ax < 3; ++ax) din[ax] = c.d_outs[i][ax];
   }
-  add("classifier.0.weight", 1, din[2]);
-  add("classifier.0.bias", 1, 0);
+  const int ncls = c.num_class >= 2 ? c.num_class : 1;   // Model.py:280: nn.Linear(128, num_class)
+  add("classifier.0.weight", ncls, din[2]);
+  add("classifier.0.bias", ncls, 0);
   const int hid = 256, emb = 128;   // Model.py:285
   const int idx4[4] = {0, 2, 4, 6};
   for (const char* n : kVmi) {

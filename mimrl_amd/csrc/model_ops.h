@@ -85,14 +85,14 @@ int tail_pre2_fwd(hipStream_t s, const float* tx_raw, float p_text, const LnSide
 // dcube[b,t,k,:] += dfeats[k][b,:]/T  for t<T
 int feat_mean_bwd(hipStream_t s, const float* dfeats, float* dcube, int B, int T, int L, int K, int D);
 
-// head: F_F[b,:] = compose_{l,k} x[b,l,k,:]; pred[b] = F_F.w + bias        (Model.py:489-515)
+// head: F_F[b,:] = compose_{l,k} x[b,l,k,:]; pred[b,c] = F_F.w[c,:] + bias[c], c < C (Model.py:280: Linear(128, num_class))   (Model.py:489-515)
 int head_fwd(hipStream_t s, const float* x, const float* w, const float* bias, float* ff, float* pred, int B, int L,
-             int K, int D, int sum_l, int sum_k);
-// dx[b,l,k,:] = scale*(dff_ext[b,:] + dpred[b]*w);  dw += sum_b dpred[b]*ff[b,:];  dbias += sum_b dpred[b]
+             int K, int D, int sum_l, int sum_k, int C = 1);
+// dx[b,l,k,:] = scale*(dff_ext[b,:] + sum_c dpred[b,c]*w[c,:]);  dw[c,:] += sum_b dpred[b,c]*ff[b,:];  dbias[c] += sum_b dpred[b,c]
 // gather (optional): dff_ext is not read; the gradient of F_F is summed from its sources on the fly (the estimators' input gradients:
 // the feature-gradient routing of the F slot folded into this kernel, one launch less on the chain)
 int head_bwd(hipStream_t s, const float* dff_ext, const float* dpred, const float* w, const float* ff, float* dx,
-             float* dw, float* dbias, int B, int L, int K, int D, int sum_l, int sum_k, const GatherSum* gather = nullptr);
+             float* dw, float* dbias, int B, int L, int K, int D, int sum_l, int sum_k, const GatherSum* gather = nullptr, int C = 1);
 
 // ---- LayerNorm along the LAST axis of [R, n] rows (D-axis mix)
 int rowln_fwd(hipStream_t s, const float* y, const float* gamma, const float* beta, float* z, float* mean, float* rstd,

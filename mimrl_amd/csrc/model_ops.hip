@@ -425,7 +425,7 @@ __global__ void feat_mean_bwd_kernel(const float* __restrict__ dfeats, float* __
 // (round 3b: 512 threads = D columns x 4 row phases for D = 128, each phase a stream of independent loads; one thread per column walking
 //  all L*K rows was an 11 us latency chain on the step's critical path)
 __global__ void head_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                float* __restrict__ ff, float* __restrict__ pred, int L, int K, int D, float scale) {
+                                float* __restrict__ ff, float* __restrict__ pred, int L, int K, int D, float scale, int C) {
   __shared__ float red[16];
   __shared__ float ph[4][128];
   const int b = blockIdx.x;
@@ -434,7 +434,7 @@ __global__ void head_fwd_kernel(const float* __restrict__ x, const float* __rest
     const int d = threadIdx.x & 127, q = threadIdx.x >> 7, n = L * K;
     ph[q][d] = head_phase_sum(x + (long)b * n * D + d, D, q, n);
     __syncthreads();
-    head_finish(ph, w, bias, ff + (long)b * D, pred + b, scale, red);
+    head_finish(ph, w, bias, ff + (long)b * D, pred + (long)b * C, scale, red, C);
     return;
   } else {
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
@@ -447,7 +447,13 @@ __global__ void head_fwd_kernel(const float* __restrict__ x, const float* __rest
     }
   }
   part = block_sum(part, red);
-  if (threadIdx.x == 0) pred[b] = part + bias[0];
+  if (threadIdx.x == 0) pred[(long)b * C] = part + bias[0];
+  for (int c = 1; c < C; ++c) {   // (the further outputs of a classification head: F_F re-read from ff, written above by the same thread)
+    part = 0.f;
+    for (int d = threadIdx.x; d < D; d += blockDim.x) part += ff[(long)b * D + d] * w[(long)c * D + d];
+    part = block_sum(part, red);
+    if (threadIdx.x == 0) pred[(long)b * C + c] = part + bias[c];
+  }
 }
 __global__ void head_bwd_kernel(const float* __restrict__ dff_ext, const float* __restrict__ dpred,
                                 const float* __restrict__ w, const float* __restrict__ ff, float* __restrict__ dx,
@@ -467,6 +473,34 @@ __global__ void head_bwd_kernel(const float* __restrict__ dff_ext, const float* 
     acc_add(&dw[d], dp * ff[(long)b * D + d]);
   }
   if (threadIdx.x == 0) acc_add(dbias, dp);
+}
+// the same for the C >= 2 outputs of a classification head: dpred [B, C], w / dw [C, D], dbias [C]
+__global__ void head_bwd_cls_kernel(const float* __restrict__ dff_ext, const float* __restrict__ dpred,
+                                    const float* __restrict__ w, const float* __restrict__ ff, float* __restrict__ dx,
+                                    float* __restrict__ dw, float* __restrict__ dbias, int L, int K, int D, float scale, GatherSum gs,
+                                    int use_gs, int C) {
+  const int b = blockIdx.x;
+  float dp[MIMRL_MAX_CLASSES];
+#pragma unroll
+  for (int c = 0; c < MIMRL_MAX_CLASSES; ++c) dp[c] = c < C ? dpred[(long)b * C + c] : 0.f;
+  for (int d = threadIdx.x; d < D; d += blockDim.x) {
+    float de = 0.f;
+    if (use_gs) {
+      for (int q = 0; q < gs.n; ++q)
+        if (b < gs.rows[q]) de += gs.src[q][(long)b * gs.ld[q] + gs.off[q] + d];
+    } else if (dff_ext) de = dff_ext[(long)b * D + d];
+    const float f = ff[(long)b * D + d];
+#pragma unroll
+    for (int c = 0; c < MIMRL_MAX_CLASSES; ++c)
+      if (c < C) {
+        de += dp[c] * w[(long)c * D + d];
+        acc_add(&dw[(long)c * D + d], dp[c] * f);
+      }
+    const float g = scale * de;
+    float* xb = dx + (long)b * L * K * D + d;
+    for (int i = 0; i < L * K; ++i) xb[(long)i * D] = g;
+  }
+  if ((int)threadIdx.x < C) acc_add(dbias + threadIdx.x, dpred[(long)b * C + threadIdx.x]);
 }
 
 // ------------------------------------------------------------------ row LayerNorm (one wave per row)
@@ -1102,19 +1136,24 @@ int feat_mean_bwd(hipStream_t s, const float* dfeats, float* dcube, int B, int T
 }
 
 int head_fwd(hipStream_t s, const float* x, const float* w, const float* bias, float* ff, float* pred, int B, int L,
-             int K, int D, int sum_l, int sum_k) {
+             int K, int D, int sum_l, int sum_k, int C) {
+  if (C < 1 || C > MIMRL_MAX_CLASSES) return set_error(MIMRL_ERR_ARG, "head_fwd: %d classes outside [1, %d]", C, MIMRL_MAX_CLASSES);
   const float scale = (sum_l ? 1.f : 1.f / L) * (sum_k ? 1.f : 1.f / K);
-  hipLaunchKernelGGL(head_fwd_kernel, dim3(B), dim3(D == 128 ? 512 : 128), 0, s, x, w, bias, ff, pred, L, K, D, scale);
+  hipLaunchKernelGGL(head_fwd_kernel, dim3(B), dim3(D == 128 ? 512 : 128), 0, s, x, w, bias, ff, pred, L, K, D, scale, C);
   LAUNCH_CHECK();
   return MIMRL_OK;
 }
 int head_bwd(hipStream_t s, const float* dff_ext, const float* dpred, const float* w, const float* ff, float* dx,
-             float* dw, float* dbias, int B, int L, int K, int D, int sum_l, int sum_k, const GatherSum* gather) {
+             float* dw, float* dbias, int B, int L, int K, int D, int sum_l, int sum_k, const GatherSum* gather, int C) {
+  if (C < 1 || C > MIMRL_MAX_CLASSES) return set_error(MIMRL_ERR_ARG, "head_bwd: %d classes outside [1, %d]", C, MIMRL_MAX_CLASSES);
   const float scale = (sum_l ? 1.f : 1.f / L) * (sum_k ? 1.f : 1.f / K);
   GatherSum gs;
   std::memset(&gs, 0, sizeof gs);
   if (gather) gs = *gather;
-  hipLaunchKernelGGL(head_bwd_kernel, dim3(B), dim3(128), 0, s, dff_ext, dpred, w, ff, dx, dw, dbias, L, K, D, scale, gs, gather ? 1 : 0);
+  if (C >= 2)
+    hipLaunchKernelGGL(head_bwd_cls_kernel, dim3(B), dim3(128), 0, s, dff_ext, dpred, w, ff, dx, dw, dbias, L, K, D, scale, gs, gather ? 1 : 0, C);
+  else
+    hipLaunchKernelGGL(head_bwd_kernel, dim3(B), dim3(128), 0, s, dff_ext, dpred, w, ff, dx, dw, dbias, L, K, D, scale, gs, gather ? 1 : 0);
   LAUNCH_CHECK();
   return MIMRL_OK;
 }

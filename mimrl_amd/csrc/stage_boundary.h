@@ -14,9 +14,10 @@ struct StageBoundaryArgs {
   float* scal; const float *mi, *cmi, *bce, *coef1;
   int *rng_step, *adam_step;
   const float *pred, *y; float* dpred; int B;
+  int C;   // classes of the head: pred / dpred are [B, C] under a classification loss (KIND >= MIMRL_CLASS_LOSS_CE)
 };
 
-// all threads of ONE workgroup (blockDim.x a multiple of 64, <= 1024); `red`: 16 floats of LDS; KIND: the task loss (MIMRL_TASK_LOSS_*)
+// all threads of ONE workgroup (blockDim.x a multiple of 64, <= 1024); `red`: 16 floats of LDS; KIND: the task loss (MIMRL_TASK_LOSS_* or MIMRL_CLASS_LOSS_*)
 template <int KIND>
 __device__ __forceinline__ void stage_boundary_body(const StageBoundaryArgs& a, float* red) {
   if (threadIdx.x == 0) {
@@ -46,7 +47,10 @@ __device__ __forceinline__ void stage_boundary_body(const StageBoundaryArgs& a, 
     *a.adam_step = as + 1;
   }
   for (int i = threadIdx.x; i < 32; i += blockDim.x) a.scal[32 + i] = 0.f;
-  task_loss_body<KIND, true>(a.pred, a.y, a.dpred, a.scal + MIMRL_S2_TASK, a.B, red);   // (behind the zeroing of scal[32..63] above)
+  if constexpr (KIND >= MIMRL_CLASS_LOSS_CE)                                             // (behind the zeroing of scal[32..63] above)
+    class_loss_body<KIND, true>(a.pred, a.y, a.dpred, a.scal + MIMRL_S2_TASK, a.B, a.C, red);
+  else
+    task_loss_body<KIND, true>(a.pred, a.y, a.dpred, a.scal + MIMRL_S2_TASK, a.B, red);
 }
 
 }  // namespace mimrl

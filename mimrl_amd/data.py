@@ -16,8 +16,10 @@ class SyntheticLoader:
     reference's default, Parameters.py:21) yields a shorter last batch."""
 
     def __init__(self, n, batch_size, T, d_t=768, d_a=74, d_v=35, seed=0, drop_last=False, device=None, ragged=False,
-                 rank=0, world=1, pin=False):
+                 rank=0, world=1, pin=False, num_class=None):
         t, a, v, y = synth.synthetic_batch(n, T, d_t, d_a, d_v, seed=seed, ragged=ragged)
+        if num_class is not None:           # --task classification: class indices derived from the regression label
+            y = synth.class_labels(y, num_class)
         if world > 1:
             per = n // world
             t, a, v, y = (x[rank::world][:per] for x in (t, a, v, y))
@@ -65,12 +67,13 @@ def get_data_loader(opt, rank=0, world=1):
         if need < 0.25 * torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory:
             device = torch.device("cuda", torch.cuda.current_device())
     k = int(getattr(opt, "k_neighbor", 2))
+    ncls = int(getattr(opt, "num_class", 1)) if getattr(opt, "task", "regression") == "classification" else None
 
     def mk(m, seed, r, w):
         if 0 < m % opt.batch_size < k:      # a last batch with fewer than k_neighbor rows has no kNN product sample (the
             m -= m % opt.batch_size          # reference's sklearn call raises on it, Model.py:85-86): do not generate one
         return SyntheticLoader(m, opt.batch_size, opt.time_len, d_t, d_a, d_v, seed=seed, drop_last=drop, rank=r, world=w, pin=pin,
-                               device=device)
+                               device=device, num_class=ncls)
 
     return (mk(n, opt.seed, rank, world), mk(max(n // 6, opt.batch_size), opt.seed + 1, 0, 1),
             mk(max(n // 3, opt.batch_size), opt.seed + 2, 0, 1), d_t, d_a, d_v)

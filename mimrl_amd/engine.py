@@ -16,6 +16,10 @@ from . import _lib
 from ._lib import Buffers, MimrlError, check
 
 
+# the task losses that are means of per-row terms (exact under data parallelism with equal shards); the rest couple the batch
+_ROW_MEAN_LOSSES = (_lib.TASK_LOSSES["MAE"], _lib.TASK_LOSSES["MSE"], _lib.CLASS_LOSSES["CE"], _lib.CLASS_LOSSES["BCE"])
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -62,7 +66,8 @@ class HipEngine:
         self.lr_critic = share.lr_critic if share else torch.full((1,), float(opt.learning_rate) * float(opt.mi_lr_rate), **f32)   # Solver.py:140-142
         # [rng step, Adam step (main), Adam step (critics), -]: optimizer / RNG state owned here like m and v
         self.counters = share.counters if share else torch.zeros(4, dtype=torch.int32, device=self.device)
-        self.pred = z(B)
+        self.num_class = max(int(self.cfg.num_class), 1)
+        self.pred = z(B) if self.num_class == 1 else z(B, self.num_class)     # logits [B, C] of a classification head
         self.feats = z(4, B, 128)
         self.scalars = z(_lib.NSCALARS)
         self.bank_rows = 0
@@ -84,8 +89,9 @@ class HipEngine:
         check(self.lib.mimrl_create(C.byref(self.cfg), C.c_void_p(self.stream.cuda_stream), C.byref(h)))
         self.handle = h
         self._bind()
-        # --loss: the handle starts at MAE; a sibling handle (``share``) keeps the loss of the engine whose optimizer it shares
-        self.task_loss = _lib.TASK_LOSSES["MAE"]
+        # --loss: the handle starts at MAE (with num_class >= 2: CE); a sibling handle (``share``) keeps the loss of the engine whose
+        # optimizer it shares
+        self.task_loss = _lib.TASK_LOSSES["MAE"] if self.num_class == 1 else _lib.CLASS_LOSSES["CE"]
         kind = share.task_loss if share is not None else _lib.task_loss_code(opt)
         if kind != self.task_loss:
             self.set_task_loss(kind)
@@ -276,21 +282,22 @@ class HipEngine:
             check(self.lib.mimrl_set_comm(self.handle, None, 1, 0))
             self.comm_world = 0
             return
-        if int(world) > 1 and self.task_loss not in (_lib.TASK_LOSSES["MAE"], _lib.TASK_LOSSES["MSE"]):
-            raise NotImplementedError("a batch-coupled task loss (RMSE, SIMSE, CCC) is the loss of the whole batch, not of one rank's shard: "
-                                      "single rank only")
+        if int(world) > 1 and self.task_loss not in _ROW_MEAN_LOSSES:
+            raise NotImplementedError("a batch-coupled task loss (RMSE, SIMSE, CCC, Focal) is the loss of the whole batch, not of one rank's "
+                                      "shard: single rank only")
         buf = (C.c_char * 128).from_buffer_copy(bytes(unique_id))
         check(self.lib.mimrl_set_comm(self.handle, C.cast(buf, C.c_void_p), int(world), int(rank)))
         self.comm_world = int(world)
         self.set_grad_scale(1.0 / world)
 
     def set_task_loss(self, kind: int):
-        """The stage-2 task loss of this handle (include/mimrl.h: mimrl_set_task_loss; ``_lib.TASK_LOSSES``): every later step, forward
-        and estimate.  Syncs; a change drops the captured graphs."""
+        """The stage-2 task loss of this handle (include/mimrl.h: mimrl_set_task_loss for ``_lib.TASK_LOSSES``, mimrl_set_class_loss for
+        ``_lib.CLASS_LOSSES``): every later step, forward and estimate.  Syncs; a change drops the captured graphs."""
         self._coherent()
-        if getattr(self, "comm_world", 0) > 1 and kind not in (_lib.TASK_LOSSES["MAE"], _lib.TASK_LOSSES["MSE"]):
-            raise NotImplementedError("a batch-coupled task loss (RMSE, SIMSE, CCC) needs the whole batch on one rank")
-        check(self.lib.mimrl_set_task_loss(self.handle, int(kind)))
+        if getattr(self, "comm_world", 0) > 1 and kind not in _ROW_MEAN_LOSSES:
+            raise NotImplementedError("a batch-coupled task loss (RMSE, SIMSE, CCC, Focal) needs the whole batch on one rank")
+        setter = self.lib.mimrl_set_class_loss if int(kind) >= _lib.CLASS_LOSSES["CE"] else self.lib.mimrl_set_task_loss
+        check(setter(self.handle, int(kind)))
         self.task_loss = int(kind)
 
     def set_comm_critic_bf16(self, on: bool):

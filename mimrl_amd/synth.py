@@ -100,6 +100,19 @@ def synthetic_batch(B: int, T: int, d_t: int = 768, d_a: int = 74, d_v: int = 35
     return t, a, v, y
 
 
+def class_labels(y: np.ndarray, num_class: int) -> np.ndarray:
+    """Class indices (float32, exactly representable) for ``--task classification``, a deterministic function of the U(-3, 3) label:
+    ``num_class`` 1 or 2: y >= 0 (the sign split of MOSI's binary task); 7: clip(round(y), -3, 3) + 3 (its seven sentiment bins);
+    otherwise the range [-3, 3] cut into ``num_class`` equal bins."""
+    y = np.asarray(y, np.float32)
+    C = int(num_class)
+    if C <= 2:
+        return (y >= 0).astype(np.float32)
+    if C == 7:
+        return (np.clip(np.round(y), -3, 3) + 3).astype(np.float32)
+    return np.clip(np.floor((y + 3.0) / 6.0 * C), 0, C - 1).astype(np.float32)
+
+
 def synthetic_banks(N: int, D: int = 128, seed: int = 0):
     """Feature banks as in the reference's own smoke test (Model.py:607): C~U(-3,3)[N,1], F,T,A,V~N(0,1)[N,D]."""
     g = _rng(f"banks:{N}", seed)
