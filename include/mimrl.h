@@ -340,6 +340,14 @@ int mimrl_op_task_loss(void* stream, int kind, const float* pred, const float* y
  * into loss[0] and, unless dlogits is NULL, dloss/dlogits into dlogits[B,C]; one workgroup, 1 <= B <= 1024, 1 <= C <= MIMRL_MAX_CLASSES;
  * CE / Focal need C >= 2, BCE C <= 2.  A label that is no integer in [0, C) is never used as an index: the loss comes out NaN. */
 int mimrl_op_class_loss(void* stream, int kind, const float* logits, const float* y, float* dlogits, float* loss, int B, int C);
+/* Row gather of up to four arrays in ONE launch (a shuffled batch: text, audio, video and labels): for every a < n_arrays (1..4) and
+ * r < rows, row_bytes[a] bytes go from src[a] + idx[r] * row_bytes[a] to dst[a] + r * row_bytes[a].  src / dst / row_bytes are HOST arrays
+ * of n_arrays entries, idx [rows] is DEVICE memory; row_bytes[a] is a positive multiple of 4 and the base addresses are 4-byte aligned
+ * (16 or 8 bytes per lane where row length and both addresses allow it).  An idx[r] outside [0, src_rows) is never used as an address:
+ * destination row r is filled with NaN in every array, the other rows are unaffected.  max_workgroups bounds the launch (so that a gather
+ * beside a running step does not occupy the whole chip); 0 = the library's choice.  Same bytes for every max_workgroups. */
+int mimrl_op_gather_rows(void* stream, int n_arrays, const void* const* src, void* const* dst, const int64_t* row_bytes, int64_t src_rows,
+                         const int32_t* idx, int rows, int max_workgroups);
 /* fused ReLU-MLP stack (critic towers VMI.py:13-22, CMI classifier Model.py:47-72), bf16 MFMA, fp32 in/out.
  * W[l] is [dims[l+1], dims[l]] row-major, group g at + g*pstride (same for b[l], db[l]); activations are
  * [nb, brows, width].  forward: act[l] (l < nl-1) = post-ReLU outputs, out = linear top layer.

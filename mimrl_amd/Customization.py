@@ -2,6 +2,7 @@
 import torch
 
 from . import _lib
+from .data import plain
 
 
 def other_model_operations(model, opt):
@@ -15,6 +16,7 @@ def compute_outputs_from_model(model, datas, opt):
     if "Dec" not in opt.dataset and opt.dataset != "synthetic":
         raise NotImplementedError(f"--dataset {opt.dataset} is not on the MI355X hot path")
     _, a_data, v_data, _, _, labels, bert_feats, bert_types, bert_mask, _, _ = datas
+    a_data, v_data, labels, bert_feats = (plain(x) for x in (a_data, v_data, labels, bert_feats))     # (a shuffling loader yields data.Rows)
     return model(bert_feats, bert_types, bert_mask, a_data, v_data, return_features=True, labels=labels)
 
 

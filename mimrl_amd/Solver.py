@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, dist as mdist, synth
+from .data import Rows, plain
 from .Customization import compute_custumized_loss, compute_outputs_from_model, other_model_operations
 from .engine import HipEngine
 from .Model import Model
@@ -218,9 +219,15 @@ class Solver:
         e = self.engine
         if self.world > 1 or not e.cfg.use_graph or not e.cfg.device_anchors or os.environ.get("MIMRL_EPOCH_PIPE", "0") in ("", "0"):
             return False
+        # eligibility is decided by LOOKING at every batch, and a look at a shuffling loader is a pass of its own (it would draw a
+        # permutation that no pass trains on, and the fallback another): such a loader takes the sequential pass, untouched
+        if getattr(self.train_loader, "shuffle", False):
+            return False
         B = e.cfg.batch
         batches = []
         for d in self.train_loader:
+            if any(isinstance(d[k], Rows) for k in (6, 1, 2, 5)):      # (a loader of its own kind that yields Rows: see above)
+                return False
             if len(d[5]) != B or not all(torch.is_tensor(d[k]) and d[k].is_cuda for k in (6, 1, 2, 5)):
                 return False
             batches.append((d[6], d[1], d[2], d[5]))
@@ -329,6 +336,7 @@ class Solver:
     def compute_loss(self, outputs, labels, stage, C_F_all, F_F_all, T_F_all, A_F_all, V_F_all):
         """Solver.py:317-342 (--loss: Utils.TASK_LOSS_FUNCTIONS) -- losses evaluated on the features of the last forward."""
         predictions = outputs[0]
+        labels = plain(labels)                     # (a shuffling loader yields data.Rows)
         labels_t = torch.as_tensor(labels, device=predictions.device).reshape(-1)
         loss_fn, C = TASK_LOSS_FUNCTIONS[self.opt.loss], int(getattr(self.opt, "num_class", 1))
         if self.opt.loss in ("Focal", "CE"):                                                     # Solver.py:324-326
@@ -384,6 +392,8 @@ class Solver:
               "banks": {k: self.engine.bank[k][:n].detach().cpu().clone() for k in "CFTAV"} if n else None}
         if self._plateau is not None:
             ck["lr_plateau"] = [(s.lr, s.best, s.num_bad_epochs) for s in self._plateau]
+        if getattr(self.train_loader, "shuffle", False):     # the pass counter of a shuffling training loader: its next permutation
+            ck["loader_pass"] = int(self.train_loader.state()["pass_index"])
         rs = np.random.get_state()
         ck["np_rng"] = (rs[0], torch.from_numpy(rs[1].astype(np.int64)), int(rs[2]), int(rs[3]), float(rs[4]))
         return ck
@@ -417,6 +427,8 @@ class Solver:
         if b is not None:
             self.engine.set_banks(*(b[k] for k in "CFTAV"))
             self.resume_banks = tuple(self.engine.bank[k][:self.engine.bank_rows] for k in "CFTAV")
+        if ck.get("loader_pass") is not None and hasattr(self.train_loader, "load_state"):
+            self.train_loader.load_state({"pass_index": int(ck["loader_pass"])})
         rs = ck.get("np_rng")
         if rs is not None:
             np.random.set_state((rs[0], rs[1].numpy().astype(np.uint32), rs[2], rs[3], rs[4]))

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import Buffers, MimrlError, check
+from .data import Rows
 
 
 # the task losses that are means of per-row terms (exact under data parallelism with equal shards); the rest couple the batch
@@ -154,11 +155,67 @@ class HipEngine:
         return {k: v.detach().clone() for k, v in self.params.items()}
 
     def set_batch(self, text, audio, video, labels):
-        """text: [B,T,d_t] post-BERT features; audio/video: [B,T,d]; labels: [B] or [B,1] (host or device tensors)."""
+        """text: [B,T,d_t] post-BERT features; audio/video: [B,T,d]; labels: [B] or [B,1] (host or device tensors), or ``data.Rows`` of
+        dataset tensors of those row shapes (a shuffled batch: gathered into the bound inputs by one launch, see ``_put_rows``)."""
+        if any(isinstance(s, Rows) for s in (text, audio, video, labels)):
+            self._put_rows((self.text, self.audio, self.video, self.labels), (text, audio, video, labels), self.stream)
+            return
         for dst, src in ((self.text, text), (self.audio, audio), (self.video, video)):
             src = torch.as_tensor(src)
             dst.copy_(src.reshape(dst.shape), non_blocking=True)
         self.labels.copy_(torch.as_tensor(labels).reshape(-1), non_blocking=True)
+
+    # workgroups of the batch gather (mimrl_op_gather_rows max_workgroups; 0 = the library's choice).  It runs on the upload stream beside
+    # a step: profiles/shuffle_epoch.json has the candidates measured at cfg2
+    GATHER_MAX_WORKGROUPS = 0
+    GATHER_ROWS = True          # False: every Rows batch goes through materialize() (index_select + copy): the A/B of tools/epoch_time.py
+
+    def _put_rows(self, dsts, srcs, stream):
+        """Enqueue, on ``stream`` (the CURRENT torch stream of the caller), the copy of a batch with ``data.Rows`` in it into the input set
+        ``dsts``.  Four Rows over device-resident bases sharing one ``idx``: ONE mimrl_op_gather_rows straight into the set, no temporary.
+        Four Rows over host bases: gathered on the host into the engine's pinned staging tensors (allocated once; reused only after the
+        upload that last read them), then the usual host-to-device copies.  Anything else (a mix of Rows and tensors, different index
+        tensors): the Rows are materialized and copied like tensors."""
+        B = dsts[3].shape[0]
+        rows = all(isinstance(s, Rows) for s in srcs)
+        if rows:
+            idx = srcs[0].idx
+            rows = all(s.idx is idx for s in srcs) and idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous()
+        if rows:
+            if len(idx) != B:
+                raise MimrlError(f"a batch of {len(idx)} rows for an engine of batch size {B}")
+            for d, s in zip(dsts, srcs):
+                b = s.base
+                if b.dtype != torch.float32 or not b.is_contiguous() or b.dim() < 1 or b.shape[0] < 1 or b.numel() // b.shape[0] != d.numel() // B:
+                    raise MimrlError(f"Rows over a {tuple(b.shape)} {b.dtype} tensor do not fit an input of shape {tuple(d.shape)}: contiguous "
+                                     f"float32 rows of the same length are needed")
+                if b.device != idx.device or b.shape[0] != srcs[0].base.shape[0]:
+                    raise MimrlError("the Rows of a batch must index datasets of one length on the device of their row numbers")
+        if rows and self.GATHER_ROWS and idx.is_cuda and self.device.index in (None, idx.device.index):
+            key = tuple(s.base.data_ptr() for s in srcs) + tuple(d.data_ptr() for d in dsts)
+            cache = self.__dict__.setdefault("_gather_args", {})
+            if key not in cache:
+                cache[key] = ((C.c_void_p * 4)(*key[:4]), (C.c_void_p * 4)(*key[4:]),
+                              (C.c_int64 * 4)(*(4 * (d.numel() // B) for d in dsts)))
+            src, dst, row_bytes = cache[key]
+            check(self.lib.mimrl_op_gather_rows(C.c_void_p(stream.cuda_stream), 4, src, dst, row_bytes, int(srcs[0].base.shape[0]),
+                                                _ptr(idx), B, int(self.GATHER_MAX_WORKGROUPS)))
+            self._gather_keep = (idx, srcs)             # alive until the next gather: the launch above reads them asynchronously
+            return
+        if rows and idx.device.type == "cpu":
+            if not hasattr(self, "_host_stage"):
+                self._host_stage = tuple(torch.empty(d.shape, dtype=d.dtype, pin_memory=True) for d in (self.text, self.audio, self.video, self.labels))
+                self._host_stage_ev = torch.cuda.Event()
+                self._host_stage_ev.record(stream)
+            self._host_stage_ev.synchronize()           # the upload that last read the staging tensors is over
+            for st, s, d in zip(self._host_stage, srcs, dsts):
+                torch.index_select(s.base.reshape(s.base.shape[0], -1), 0, idx, out=st.view(B, -1))
+                d.copy_(st, non_blocking=True)
+            self._host_stage_ev.record(stream)
+            return
+        for d, s in zip(dsts, srcs):
+            s = s.materialize() if isinstance(s, Rows) else torch.as_tensor(s)
+            d.copy_(s.reshape(d.shape), non_blocking=True)
 
     def set_banks(self, C_all, F_all, T_all, A_all, V_all):
         """Previous epoch's stage-2 labels/features (Solver.py:223-227,244).  Empty => epoch-0 rule."""
@@ -471,7 +528,8 @@ class HipEngine:
 
     def stage_batch(self, text, audio, video, labels):
         """Start the host->device copy of the NEXT batch into the IDLE input set on a copy stream (it overlaps the step that
-        is running on the active set).  Sources in pinned memory make the copy truly asynchronous."""
+        is running on the active set).  Sources in pinned memory make the copy truly asynchronous.  ``data.Rows`` sources (a shuffled
+        batch) are gathered into the idle set on the same stream under the same events (``_put_rows``)."""
         self._ensure_sets()
         idle = 1 - self._active
         # steps that read the idle set have finished.  A HOST wait (the caller runs at most one step ahead of the device), not
@@ -482,8 +540,11 @@ class HipEngine:
         with torch.cuda.stream(self._copy_stream):
             if self._upload_legacy:
                 self._copy_stream.wait_event(self._free_ev[idle])
-            for dst, src in zip(self._sets[idle], (text, audio, video, labels)):
-                dst.copy_(torch.as_tensor(src).reshape(dst.shape), non_blocking=True)
+            if any(isinstance(s, Rows) for s in (text, audio, video, labels)):
+                self._put_rows(self._sets[idle], (text, audio, video, labels), self._copy_stream)
+            else:
+                for dst, src in zip(self._sets[idle], (text, audio, video, labels)):
+                    dst.copy_(torch.as_tensor(src).reshape(dst.shape), non_blocking=True)
             self._staged_ev.record(self._copy_stream)
 
     def commit_batch(self):
@@ -501,7 +562,7 @@ class HipEngine:
     # ------------------------------------------------------------------ epoch-ordered critic pass with look-ahead forward (round 6)
     def stage1_pass(self, batches, on_step=None):
         """One pass of critic updates (reference: the inner loop of Solver.py:200-216) over ``batches`` = an iterable of
-        ``(text, audio, video, labels)`` DEVICE tensors of this engine's batch size.  The main model is frozen in such a pass, so
+        ``(text, audio, video, labels)`` DEVICE tensors (or ``data.Rows`` of resident datasets) of this engine's batch size.  The main model is frozen in such a pass, so
         Model.forward of batch i + 1 runs beside the estimators / clip / Adam of batch i (`mimrl_stage1_pipe`): the next batch is copied
         into the idle input set (device to device, on the engine's stream) in front of the step on the current one.  ``on_step(self)`` is
         called behind every enqueued step (the caller accumulates ``self.scalars`` there).  Same losses, dropout masks and anchor draws as
@@ -512,6 +573,8 @@ class HipEngine:
         if cur is None:
             return 0
         def put(slot, b):
+            if any(isinstance(s, Rows) for s in b):
+                return self._put_rows(self._sets[slot], tuple(b), self.stream)
             for dst, src in zip(self._sets[slot], b):
                 dst.copy_(torch.as_tensor(src).reshape(dst.shape), non_blocking=True)
         def bind(slot):
