@@ -72,6 +72,7 @@ int concat_fwd_ws(hipStream_t s, const ConcatFwdArgs& a);
 bool concat_bwd_ws_supported(int B, int hid);
 long concat_bwd_ws_scratch(int E, int B);
 int concat_bwd_ws(hipStream_t s, const ConcatBwdArgs& a);
+bool concat_bwd_runs_ws(const ConcatBwdArgs& a);   // will concat_bwd_fused route these arguments there?  (reads MIMRL_CONCAT_STREAMED, per call, as the dispatch does)
 int concat_fwd_ws4(hipStream_t s, const ConcatFwdArgs& a);   // tools/hw/concat_ws4.hip (experiment, not in the library): one wave per SIMD
 // dw3[e] += ds[e]^T a2[e]  (compact saves: concat_bwd_fused leaves the score head's weight gradient to this streaming launch)
 int concat_dw3(hipStream_t s, const float* ds, const float* a2, float* dw3, int E, int B, long pstride, bool a2_f16 = false);

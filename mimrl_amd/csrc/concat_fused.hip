@@ -561,6 +561,10 @@ long concat_bwd_dq_scratch(int E, int B) {
 
 bool concat_bwd_fused_supported(int B, int hid) { return hid == CH && B >= CR && B % CR == 0; }
 
+bool concat_bwd_runs_ws(const ConcatBwdArgs& a) {
+  return a.dQ && a.compact && a.dq_part && concat_bwd_ws_supported(a.B, CH) && !knob_on("MIMRL_CONCAT_STREAMED");
+}
+
 int concat_bwd_fused(hipStream_t s, const ConcatBwdArgs& a) {
   if (!concat_bwd_fused_supported(a.B, CH)) return set_error(MIMRL_ERR_ARG, "concat_bwd_fused: batch %d unsupported", a.B);
   if (!(a.dz0 || a.dQ) || !a.dP || !a.ds) return set_error(MIMRL_ERR_ARG, "concat_bwd_fused: null argument");
@@ -570,7 +574,7 @@ int concat_bwd_fused(hipStream_t s, const ConcatBwdArgs& a) {
     return set_error(MIMRL_ERR_ARG, "concat_bwd_fused: the weight-gradient outputs come together");
   const bool wg = a.dz2 != nullptr;
   // round 6: the weights-stationary kernel (concat_ws_bwd.hip) wherever the in-kernel dQ reduction is on; MIMRL_CONCAT_STREAMED=1: the kernel below
-  if (a.dQ && a.compact && a.dq_part && concat_bwd_ws_supported(a.B, CH) && !knob_on("MIMRL_CONCAT_STREAMED")) return concat_bwd_ws(s, a);
+  if (concat_bwd_runs_ws(a)) return concat_bwd_ws(s, a);
   if (a.dQ) {   // runs of tiles with dQ in registers: one workgroup per CU, ceil(tiles / CUs) tiles each
     if (!a.compact || !a.dq_part) return set_error(MIMRL_ERR_ARG, "concat_bwd_fused: the in-kernel dQ reduction needs the compact saves and its scratch");
     int per = 0, nwg = 0, slots = 0;

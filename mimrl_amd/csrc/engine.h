@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <string>
 #include <vector>
 #include <dlfcn.h>
 
@@ -102,6 +103,60 @@ struct MixBuf { float *xn = nullptr, *xn_mean = nullptr, *xn_rstd = nullptr, *u 
                       *z = nullptr, *mean = nullptr, *rstd = nullptr; };
 struct BlockBuf { MixBuf l, k, d; };
 
+// Every decision the engine takes from the environment (knobs.h), read ONCE per handle by read_switches (engine_abi.hip, beside
+// mimrl_create) and held by the handle as `const Switches sw`: two engines with different settings can live in one process, and nothing
+// on the step path reads the environment.  All are tuning / debugging switches; the defaults are what bench.py measures.  (Not here:
+// MIMRL_DDP_SPLIT, read when the communicator is attached (mimrl_set_comm); the knobs of gru.hip, gemm_tall.hip, lstm.hip, mlp_fused.hip
+// and concat_fused.hip, which those files read themselves.)  "set" below means set to anything, "0" included.
+struct Switches {
+  bool multi_stream;     // MIMRL_SINGLE_STREAM set: everything on one stream (initial value of mimrl_handle::multi_stream)
+  bool fused_cube;       // bf16 mode: CubeMLP blocks as one LDS-resident kernel (MIMRL_NO_FUSED_CUBE set: the unfused GEMM / LayerNorm chain)
+  bool fused_cube_bwd;   // bf16 mode: per-axis fused data-gradient chains of CubeMLP (MIMRL_NO_FUSED_CUBE_BWD set: the unfused chain)
+  bool fused_pre;        // short sequences: the pre-CubeMLP pieces of a forward tail as one pass (MIMRL_NO_FUSED_TAIL_PRE set, but not to 2: three launches) ...
+  bool cube_bookends;    // ... which is block 0's tile load, and the head the last block's epilogue, where those blocks are fused
+                         // (MIMRL_NO_FUSED_TAIL_PRE=2: tail_pre / head_fwd stay launches around them)
+  bool fused_mlp;        // bf16 mode: estimator MLP stacks as one kernel per direction (MIMRL_NO_FUSED_MLP set: grouped GEMMs)
+  bool fused_mlp_bwd;    // ... their data-gradient chain too (MIMRL_NO_FUSED_MLP_BWD set: GEMMs)
+  bool fused_mi;         // separable critic: scores / bound / gradients in mi_sep_fused / mi_sep_nce (MIMRL_NO_FUSED_MI set: separate kernels)
+  bool mi_nce_tiled;     // separable InfoNCE: the row-tiled kernel (MIMRL_NO_MI_NCE_TILED set: one workgroup per estimator)
+  bool fused_concat;     // concat critic forward as one launch, concat_fused.hip (MIMRL_NO_FUSED_CONCAT set: pair_expand + three GEMMs)
+  bool concat_dq;        // concat critic backward: dQ partial sums inside the kernel (MIMRL_NO_CONCAT_DQ set: fp32 dZ0 + pair_reduce_q, rounds 2-4)
+  bool concat_dw;        // concat critic: the hidden-layer weight gradients as one launch, concat_dw.hip (MIMRL_NO_CONCAT_DW set: two split-K GEMMs)
+  bool fold_unpack;      // the packed layer-0 GRU weight gradients are scattered by the Adam launch (MIMRL_NO_FOLD_UNPACK set: the separate l0_unpack kernel)
+  bool h16;              // fp16 / bf16 operands for the layer-1 projection and dh0 (MIMRL_NO_H16 set: fp32-stored operands; bit-identical results)
+  bool xin;              // the layer-0 input projection inside the recurrence kernel (MIMRL_NO_XIN set: its own GEMM)
+  bool rec16;            // the BPTT launches read 16-bit dout / h_prev (MIMRL_REC16=0: fp32, round 5a)
+  bool dwih_h16;         // the layer-1 dW_ih product reads the recurrence's fp16 copy of the layer-0 outputs (MIMRL_DWIH_H16=0: the fp32 outputs)
+  bool laxis_long;       // L > 64: the L-axis MLP as the one-pass kernel of cube_long.hip (MIMRL_LAXIS_LONG=0: the GEMM chain)
+  bool laxis_bwd_long;   // L > 64: the LONG instantiation of laxis_bwd_kernel (MIMRL_LAXIS_BWD_LONG=0: colln_bwd + GEMM chain)
+  bool adam_frag;        // combined step: frag_images + stage_boundary inside the critic Adam launch (MIMRL_ADAM_FRAG=0: launches behind it, round 5a)
+  bool gru_wgrad;        // long sequences: the layer-0 GRU weight gradients as the one-pass kernel of gru_wgrad.hip (MIMRL_NO_GRU_WGRAD set: two batched split-K GEMMs)
+  bool shared_prefix;    // prefetch mode: the encoder prefix evaluated once for both stages (MIMRL_NO_SHARED_PREFIX set: twice)
+  bool dual_tail_pre;    // T > 128: the pre-CubeMLP pieces of both forward tails in one launch (MIMRL_NO_DUAL_TAIL_PRE set: each tail its own)
+  bool step_graph;       // Solver.step as ONE captured graph (MIMRL_NO_STEP_GRAPH set: two per-stage graphs)
+  int fwd_f16;           // bf16 mode: the forward products in front of / inside CubeMLP round their operands to FP16, not bf16
+                         // (GemmDesc::f16, cube_fused.hip: main-gradient cosine vs fp32 0.964 -> 0.998); MIMRL_FWD_BF16 set: 0
+  // packed layer-0 operands (MIMRL_L0_PACK=0: off): one batched projection + two batched weight gradients instead of 2 + 4 launches: the
+  // four layer-0 weight-gradient GEMMs in a row are what closes the stage behind the BPTT.  (History: before the parked CubeMLP weight
+  // gradients became two grouped launches the side streams were the bottleneck and packing lost at cfg2, 1.34 vs 1.32 ms; since then it
+  // wins, 1.14 vs 1.18 ms.)
+  bool l0_packed;
+  // BPTT outputs dg[B,T,4H] / h_prev stored as bf16 (GRU encoders with bf16 recurrence + bf16 backward GEMMs; MIMRL_DG_FP32 set: fp32).
+  // They are consumed only by GEMMs that round their operands to bf16 anyway: storing them as bf16 changes no number in this mode and
+  // halves what the BPTT writes and the weight-gradient / dh0 products read
+  bool dg_bf16;
+  // gx[B,T,3H] -- written once by the input projection, read once by the recurrence -- as fp16 (MIMRL_GX_F16=1 with GRU encoders, bf16
+  // recurrence + bf16 forward GEMMs; OFF by default).  Round 4 built it for cfg3, whose two projections on the chain are bound by 786 MB
+  // of fp32 stores each (449 / 302 us), and measured a LOSS: 7.24 against 6.83 ms per step.  The accumulator layout gives a lane one
+  // column of 16 rows, so an fp16 store instruction writes two 64-byte half lines (fp32: two full 128-byte lines): half the bytes, but
+  // partial-line writes.  Winning needs the tile staged through LDS and written back as whole rows -- a different epilogue.  The path
+  // stays (tests/test_gpu_fused_oracle.py holds it to the rounded oracle).
+  bool gx_f16;
+  int dbg_delay_tag, dbg_delay_us;   // MIMRL_DBG_DELAY_TAG=<tag>[:<us>]: critical-path probe (dbg_delay); tag -1 = off, 50 us unless given
+  std::string graph_dot;             // MIMRL_GRAPH_DOT: file the captured two-stage graph is dumped to (empty: no dump); a copy, since a later setenv may invalidate getenv's pointer
+};
+Switches read_switches(const mimrl_cfg& cfg);   // engine_abi.hip
+
 }  // namespace eng
 
 using namespace eng;
@@ -112,6 +167,8 @@ using namespace mimrl;
 
 struct mimrl_handle {
   mimrl_cfg cfg;
+  const Switches sw;                   // what the environment decided when the handle was created; never written again
+  explicit mimrl_handle(const mimrl_cfg& c) : cfg(c), sw(read_switches(c)) {}
   hipStream_t stream = nullptr;        // stream every launch goes to (the caller's, or cap_stream while capturing)
   hipStream_t user_stream = nullptr;   // the caller's stream (graphs are launched here)
   hipStream_t cap_stream = nullptr;    // private non-default stream: capture is illegal on the legacy default stream
@@ -142,11 +199,9 @@ struct mimrl_handle {
   bool frag_side_pending = false;      // the refresh behind the critic Adam runs on side 3 and has not been joined yet
   bool frag_tr_deferred = false;       // the data-gradient fragment images are still to be launched (enqueue_apply -> estimators_all: ftab_tr)
   FragTable ftab_tr;
-  bool adam_frag_on = true;            // MIMRL_ADAM_FRAG=0 (mimrl_create)
   bool boundary_in_adam = false;       // the stage boundary rode on the critic Adam launch (enqueue_apply -> run)
   bool img_valid = false;
   unsigned knn_ovr_mask[2] = {0u, 0u};  // per stage: CMI calls whose neighbour rows come from bufs.knn_override
-  bool knn_pre = true;                 // prefetch mode: stage 2's kNN sampling also runs inside stage 1, beside the encoder prefix
   bool mi_fused_bwd_done = false;      // mi_forward already produced the tower-output gradients (mi_sep_fused)
   bool imgT_ready = false;             // a transposed-image refresh has been issued for the estimator pass being enqueued
   TransposeTable ttab;
@@ -192,27 +247,18 @@ struct mimrl_handle {
   // the four W_ih_l1 written by the layer-0 pack launch of the same forward pass
   _Float16* h0h[2] = {nullptr, nullptr}; _Float16* w1h = nullptr; __bf16* w1b = nullptr;
   __bf16* w1bt = nullptr;              // w1b transposed + direction-concatenated [modality][256][768]: B operand of the tall (k-contiguous) dh0 product
-  bool h16_on = true;                  // MIMRL_NO_H16=1: fp32 operands as before (tuning knob; results are bit-identical either way)
   float* w2p[MIMRL_MAX_BLOCKS] = {};   // unfused L axis: fc2 [ol, hl] copied to row pitch roundup4(hl) when hl % 4 != 0 (GemmDesc::a_pad4)
   bool w2p_valid[MIMRL_MAX_BLOCKS] = {};   // ... holds the current parameters (set by the forward pass, cleared by the main update)
-  bool xin_on = true;                  // MIMRL_NO_XIN=1: the layer-0 input projection as its own GEMM (tuning knob)
   bool part0_done = false;             // mimrl_stage_grads_part(h, 2, 0) ran on the bound batch and nothing since: part 1 may follow
   bool l0_xin = false;                 // this step's layer-0 forward ran the fused-projection (8-wave) kernel: its BPTT launch must match
   bool xpack16 = false;                // the packed layer-0 operands of this step are the 16-bit arrays (set by the forward pass)
-  bool laxis_bwd_long_on = true;       // MIMRL_LAXIS_BWD_LONG=0 (mimrl_create): colln_bwd + GEMM chain for the L-axis backward of long sequences
-  bool laxis_long_on = true;           // MIMRL_LAXIS_LONG=0 (mimrl_create): the GEMM chain for the L axis of long sequences
-  bool rec16_on = true, dwih_h16_on = true;   // MIMRL_REC16=0 / MIMRL_DWIH_H16=0 (mimrl_create)
   bool hp16_live = false;              // this pass's layer-0 BPTT reads h_prev from h0h (set by the forward pass; with the fused projection the fp32 outputs were not even written)
   bool dh0_bf16_live = false, ds_bf16_live = false;   // this pass's dh0 / ds were written as bf16 (gru_layer_backward / encoders_backward -> the BPTT launches)
   bool h16_live = false;               // h0h holds the fp16 copy of THIS pass's layer-0 outputs (set by the forward pass)
   bool w1_img_valid = false;           // w1b holds the CURRENT main parameters (set by the forward pass, cleared by the main update)
   int KP() const { return ((cfg.d_a > cfg.d_v ? cfg.d_a : cfg.d_v) + 15) & ~15; }
-  bool dg_bf16 = false;                // BPTT outputs dg / h_prev stored as bf16 (GRU encoders, bf16 recurrence + bf16 backward GEMMs; MIMRL_DG_FP32=1: off)
   bool concat_compact = false;         // the last concat forward saved bitmasks (+ bf16 values) for the fused backward, not fp32 activations
   bool a0_regen_live = false;         // stage 1's concat forward did not save a0 (round 6b): concat_dw regenerates it from P and Q
-  bool fused_concat = true;            // concat critic forward as one launch (concat_fused.hip); MIMRL_NO_FUSED_CONCAT=1 at create time
-  bool l0_packed = false;              // see mimrl_create
-  bool l0_bwd_pack = false;            // small batches: only the INPUTS are packed (off the chain) and only the weight gradients use them
   BlockBuf bb[MIMRL_MAX_BLOCKS];
   __bf16* wtT[MIMRL_MAX_BLOCKS][3] = {};   // transposed bf16 images of the D-axis weights (fc2, fc1, res) for the fused backward
   // Second set of forward buffers.  In prefetch mode (mimrl_set_stage2_prefetch) stage 1 runs its forward pass and its
@@ -272,8 +318,6 @@ struct mimrl_handle {
   float *cP = nullptr, *cQ = nullptr, *ca[3];
   int split_part = 0;                  // 1: encoders_backward stops behind the layer-1 weight gradients (mimrl_stage_grads_part); 0: whole pass
   bool fold_unpack = false, unpack_pending = false;   // the packed layer-0 GRU weight gradients are scattered by the Adam launch (AdamArgs::fold)
-  bool fold_unpack_on = true;          // MIMRL_NO_FOLD_UNPACK=1: keep the separate scatter kernel (tuning knob)
-  bool gx_f16 = false;                 // the hoisted GRU input projections gx[B,T,3H] are stored as fp16 (long sequences, bf16 mode: create)
   int *knn_idx = nullptr, *knn_idx2 = nullptr;   // neighbour indices; stage 2 has its own set (prefetch mode samples it early)
   // which of the two anchor / neighbour-index sets a stage uses: its own -- except inside a pipelined critic pass (mimrl_stage1_pipe), where stage 1
   // alternates between both (the sampler of the NEXT call runs beside this call's estimators; stage 2 is not running then)
@@ -296,16 +340,8 @@ struct mimrl_handle {
   hipStream_t side[NSIDE] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   std::vector<hipEvent_t> ev_pool;
   size_t ev_next = 0;
-  bool multi_stream = true;
-  bool fused_cube_bwd = true;          // bf16 mode: per-axis fused data-gradient chains of CubeMLP (MIMRL_NO_FUSED_CUBE_BWD=1 disables)
-  bool fused_mlp = true;               // bf16 mode: estimator MLP stacks as one kernel per direction (MIMRL_NO_FUSED_MLP=1 disables)
-  bool fused_cube = true;              // bf16 mode: CubeMLP blocks as one LDS-resident kernel (MIMRL_NO_FUSED_CUBE=1 disables)
-  bool fused_pre_on = true;            // short sequences: the pre-CubeMLP pieces of a forward tail as one pass (MIMRL_NO_FUSED_TAIL_PRE=1: three launches) ...
-  bool cube_bookends = true;           // ... which is block 0's tile load, and the head the last block's epilogue, where those blocks are fused (MIMRL_NO_FUSED_TAIL_PRE=2:
-                                       // tail_pre / head_fwd stay launches around them).  Both read when the handle is created.
+  bool multi_stream = true;            // sw.multi_stream (deterministic build: false) between calls; mutable because a Hold narrows it to one stream for a branch
   bool keep_cube0 = false;             // a forward pass without saved activations still writes the fp32 cube0 (mimrl_probe_encoders reads it)
-  int fwd_f16 = 1;                     // bf16 mode: the forward products in front of / inside CubeMLP round their operands to FP16, not bf16
-                                       // (GemmDesc::f16, cube_fused.hip: main-gradient cosine vs fp32 0.964 -> 0.998); MIMRL_FWD_BF16=1: off
   int next_event(hipEvent_t* e) {
     if (ev_next == ev_pool.size()) {
       hipEvent_t n;
@@ -443,7 +479,7 @@ struct mimrl_handle {
         for (CachedGraph& c : gsets[q].all) retire(c.exec);
   }
   // Replay the graph cached in `slot`; captured first from what `body` enqueues on `stream` when the slot is empty or holds another bank size
-  // (engine_step.hip).  postprocess: the MIMRL_GRAPH_DOT dump of the step graph.
+  // (engine_step.hip).  postprocess: the dump of the step graph (sw.graph_dot).
   template <typename Body>
   int replay_or_capture(CachedGraph& slot, Body&& body, bool postprocess = false);
   float* P(long off) const { return bufs.main_p + off; }
@@ -489,7 +525,7 @@ struct mimrl_handle {
   std::vector<Deferred> deferred;
   int flush_deferred(int only_side = 0);
   int wg_helper = -1;                  // side stream for weight-gradient GEMMs of an MLP stack beside the data-gradient chain / the grouped launch (-1: none)
-  int dbg_delay(hipStream_t st, int tag);   // critical-path probe (MIMRL_DBG_DELAY_TAG / _US): a spin kernel behind one phase
+  int dbg_delay(hipStream_t st, int tag);   // critical-path probe (sw.dbg_delay_tag / _us): a spin kernel behind one phase
   int model_forward(bool train, bool save, int knn_stage = 0, int part = 0);   // part: 0 all, 1 prefix, 2 tail
   int cube_forward(bool train, bool save, const CubePre* pre = nullptr, const CubeHead* head = nullptr);   // pre / head: fold the tail's bookends into block 0 / the last block
   bool cube_block_fused(int i, bool train) const;   // block i of cube_forward takes the one-kernel path (cube_fused.hip)

@@ -28,6 +28,57 @@ int mimrl_device_check(void) {
   return MIMRL_OK;
 }
 
+}  // extern "C"
+
+// The one place where the engine reads its knobs (engine.h: struct Switches says what each field selects); mimrl_handle's constructor
+// calls it.  Apart from it only MIMRL_KNOBS (mimrl_create) and MIMRL_DDP_SPLIT (mimrl_set_comm) are read in engine_*.hip.
+Switches mimrl::eng::read_switches(const mimrl_cfg& cfg) {
+  Switches sw;
+  sw.multi_stream = knob("MIMRL_SINGLE_STREAM") == nullptr;
+  sw.fused_cube = knob("MIMRL_NO_FUSED_CUBE") == nullptr;
+  sw.fused_cube_bwd = knob("MIMRL_NO_FUSED_CUBE_BWD") == nullptr;
+  {
+    const char* v = knob("MIMRL_NO_FUSED_TAIL_PRE");
+    const bool keep_launches = v && v[0] == '2' && v[1] == 0;
+    sw.fused_pre = v == nullptr || keep_launches;
+    sw.cube_bookends = v == nullptr;
+  }
+  sw.fused_mlp = knob("MIMRL_NO_FUSED_MLP") == nullptr;
+  sw.fused_mlp_bwd = knob("MIMRL_NO_FUSED_MLP_BWD") == nullptr;
+  sw.fused_mi = knob("MIMRL_NO_FUSED_MI") == nullptr;
+  sw.mi_nce_tiled = knob("MIMRL_NO_MI_NCE_TILED") == nullptr;
+  sw.fused_concat = knob("MIMRL_NO_FUSED_CONCAT") == nullptr;
+  sw.concat_dq = knob("MIMRL_NO_CONCAT_DQ") == nullptr;
+  sw.concat_dw = knob("MIMRL_NO_CONCAT_DW") == nullptr;
+  sw.fold_unpack = knob("MIMRL_NO_FOLD_UNPACK") == nullptr;
+  sw.h16 = knob("MIMRL_NO_H16") == nullptr;
+  sw.xin = knob("MIMRL_NO_XIN") == nullptr;
+  sw.rec16 = knob_int("MIMRL_REC16", 1) != 0;
+  sw.dwih_h16 = knob_int("MIMRL_DWIH_H16", 1) != 0;
+  sw.laxis_long = knob_int("MIMRL_LAXIS_LONG", 1) != 0;
+  sw.laxis_bwd_long = knob_int("MIMRL_LAXIS_BWD_LONG", 1) != 0;
+  sw.adam_frag = knob_int("MIMRL_ADAM_FRAG", 1) != 0;
+  sw.gru_wgrad = knob("MIMRL_NO_GRU_WGRAD") == nullptr;
+  sw.shared_prefix = knob("MIMRL_NO_SHARED_PREFIX") == nullptr;
+  sw.dual_tail_pre = knob("MIMRL_NO_DUAL_TAIL_PRE") == nullptr;
+  sw.step_graph = knob("MIMRL_NO_STEP_GRAPH") == nullptr;
+  sw.fwd_f16 = knob("MIMRL_FWD_BF16") == nullptr;
+  sw.l0_packed = knob_int("MIMRL_L0_PACK", 1) != 0;
+  const bool gru = cfg.encoder == MIMRL_ENCODER_GRU;
+  sw.dg_bf16 = gru && (cfg.precision & MIMRL_PREC_BF16_GRU_BWD) && (cfg.precision & MIMRL_PREC_BF16_GEMM_BWD) && knob("MIMRL_DG_FP32") == nullptr;
+  sw.gx_f16 = gru && (cfg.precision & MIMRL_PREC_BF16_GRU_FWD) && (cfg.precision & MIMRL_PREC_BF16_GEMM_FWD) && knob_int("MIMRL_GX_F16", 0) != 0;
+  {
+    const char* spec = knob("MIMRL_DBG_DELAY_TAG");
+    const char* colon = spec ? strchr(spec, ':') : nullptr;
+    sw.dbg_delay_tag = spec ? atoi(spec) : -1;
+    sw.dbg_delay_us = colon ? atoi(colon + 1) : 50;
+  }
+  if (const char* dot = knob("MIMRL_GRAPH_DOT")) sw.graph_dot = dot;
+  return sw;
+}
+
+extern "C" {
+
 int mimrl_create(const mimrl_cfg* cfg, void* hip_stream, mimrl_handle** out) {
   if (!cfg || !out) return set_error(MIMRL_ERR_ARG, "null argument");
   *out = nullptr;
@@ -46,61 +97,18 @@ int mimrl_create(const mimrl_cfg* cfg, void* hip_stream, mimrl_handle** out) {
 #endif
   MX(mimrl_device_check());
   if (knob_on("MIMRL_KNOBS")) knobs_print(stderr);
-  mimrl_handle* h = new (std::nothrow) mimrl_handle();
+  mimrl_handle* h = new (std::nothrow) mimrl_handle(*cfg);   // (its constructor reads the environment: read_switches)
   if (!h) return set_error(MIMRL_ERR_STATE, "out of host memory");
-  h->cfg = *cfg;
   if (h->ncls() >= 2) h->task_loss = MIMRL_CLASS_LOSS_CE;   // (a regression loss has no meaning on [B, num_class] logits)
   if (h->cfg.beta1 == 0.f) h->cfg.beta1 = 0.9f;
   if (h->cfg.beta2 == 0.f) h->cfg.beta2 = 0.999f;
   if (h->cfg.adam_eps == 0.f) h->cfg.adam_eps = 1e-8f;
   h->stream = h->user_stream = reinterpret_cast<hipStream_t>(hip_stream);
-  h->multi_stream = knob("MIMRL_SINGLE_STREAM") == nullptr;
+  h->multi_stream = h->sw.multi_stream;
 #ifdef MIMRL_DET
   h->multi_stream = false;   // deterministic build: one stream, so the flush behind a launch never meets a half-finished producer (det.h)
   MX(det_init());
 #endif
-  h->fused_cube = knob("MIMRL_NO_FUSED_CUBE") == nullptr;
-  {   // per handle (not a function-local static): two engines with different settings can live in one process
-    const char* v = knob("MIMRL_NO_FUSED_TAIL_PRE");
-    const bool keep_launches = v && v[0] == '2' && v[1] == 0;
-    h->fused_pre_on = v == nullptr || keep_launches;
-    h->cube_bookends = v == nullptr;
-  }
-  h->fused_mlp = knob("MIMRL_NO_FUSED_MLP") == nullptr;
-  h->knn_pre = true;
-  h->fold_unpack_on = knob("MIMRL_NO_FOLD_UNPACK") == nullptr;
-  h->h16_on = knob("MIMRL_NO_H16") == nullptr;
-  h->xin_on = knob("MIMRL_NO_XIN") == nullptr;
-  h->fused_cube_bwd = knob("MIMRL_NO_FUSED_CUBE_BWD") == nullptr;
-  h->laxis_bwd_long_on = !(knob("MIMRL_LAXIS_BWD_LONG") && atoi(knob("MIMRL_LAXIS_BWD_LONG")) == 0);
-  h->laxis_long_on = !(knob("MIMRL_LAXIS_LONG") && atoi(knob("MIMRL_LAXIS_LONG")) == 0);
-  h->rec16_on = !(knob("MIMRL_REC16") && atoi(knob("MIMRL_REC16")) == 0);
-  h->dwih_h16_on = !(knob("MIMRL_DWIH_H16") && atoi(knob("MIMRL_DWIH_H16")) == 0);
-  h->adam_frag_on = !(knob("MIMRL_ADAM_FRAG") && atoi(knob("MIMRL_ADAM_FRAG")) == 0);
-  // opt-in (measured slower at cfg2, 0.814-0.819 vs 0.799-0.800 ms: the parked block-0 weight gradients then start together with the layer-1 BPTT
-  // instead of 30 us ahead of it, and the BPTT beside them takes 74 instead of 53 us -- DESIGN section 7)
-  h->fused_concat = knob("MIMRL_NO_FUSED_CONCAT") == nullptr;
-  h->fwd_f16 = knob("MIMRL_FWD_BF16") == nullptr;
-  // packed layer-0 operands: one batched projection + two batched weight gradients instead of 2 + 4 launches: the four layer-0
-  // weight-gradient GEMMs in a row are what closes the stage behind the BPTT.  (History: before the parked CubeMLP weight gradients
-  // became two grouped launches the side streams were the bottleneck and packing lost at cfg2, 1.34 vs 1.32 ms; since then it
-  // wins, 1.14 vs 1.18 ms.)  MIMRL_L0_PACK=0 / 1 forces it.
-  h->l0_packed = knob("MIMRL_L0_PACK") ? atoi(knob("MIMRL_L0_PACK")) != 0 : true;
-  // (inputs packed on side 0, only the layer-0 weight gradients batched: MIMRL_L0_BWD_PACK=1 with MIMRL_L0_PACK=0; 1.15 ms at cfg2)
-  // dg[B,T,4H] / h_prev are consumed only by GEMMs that round their operands to bf16 anyway: storing them as bf16 changes no
-  // number in this mode and halves what the BPTT writes and the weight-gradient / dh0 products read
-  h->dg_bf16 = cfg->encoder == MIMRL_ENCODER_GRU && (cfg->precision & MIMRL_PREC_BF16_GRU_BWD) && (cfg->precision & MIMRL_PREC_BF16_GEMM_BWD) &&
-               knob("MIMRL_DG_FP32") == nullptr;
-  h->l0_bwd_pack = false;
-  // gx[B,T,3H] -- written once by the input projection, read once by the recurrence -- as fp16 (MIMRL_GX_F16=1; OFF by default).  Round 4
-  // built it for cfg3, whose two projections on the chain are bound by 786 MB of fp32 stores each (449 / 302 us), and measured a LOSS:
-  // 7.24 against 6.83 ms per step.  The accumulator layout gives a lane one column of 16 rows, so an fp16 store instruction writes two
-  // 64-byte half lines (fp32: two full 128-byte lines): half the bytes, but partial-line writes.  Winning needs the tile staged through LDS
-  // and written back as whole rows -- a different epilogue.  The path stays (tests/test_gpu_fused_oracle.py holds it to the rounded oracle).
-  {
-    const bool can = cfg->encoder == MIMRL_ENCODER_GRU && (cfg->precision & MIMRL_PREC_BF16_GRU_FWD) && (cfg->precision & MIMRL_PREC_BF16_GEMM_FWD);
-    h->gx_f16 = can && knob("MIMRL_GX_F16") && atoi(knob("MIMRL_GX_F16")) != 0;
-  }
   if (cfg->encoder == MIMRL_ENCODER_GRU && ((cfg->precision & MIMRL_PREC_BF16_GRU_FWD) != 0) != ((cfg->precision & MIMRL_PREC_BF16_GRU_BWD) != 0)) {
     mimrl_destroy(h);   // the forward kernel writes the gate slab in the format (bf16 / fp32 records) the BPTT kernel of the SAME mode reads
     return set_error(MIMRL_ERR_ARG, "MIMRL_PREC_BF16_GRU_FWD and MIMRL_PREC_BF16_GRU_BWD must be set together");
@@ -304,7 +312,7 @@ int mimrl_probe_mi(mimrl_handle* h, int stage, float* mi, float* scores, float* 
   h->ev_next = 0;
   MX(h->ensure_images());
   h->imgT_ready = false;
-  if (bf_bwd && h->fused_mlp && h->crit_imgT && h->ttab.n > 0) {   // as estimators_all does, but in line
+  if (bf_bwd && h->sw.fused_mlp && h->crit_imgT && h->ttab.n > 0) {   // as estimators_all does, but in line
     MX(bf16_transposed_images(h->stream, h->bufs.crit_p, h->crit_imgT, h->ttab));
     h->imgT_ready = true;
   }
@@ -339,7 +347,7 @@ int mimrl_probe_cmi(mimrl_handle* h, int stage, const float* cmi_in_, float* log
   h->ev_next = 0;
   MX(h->ensure_images());
   h->imgT_ready = false;
-  if (bf_bwd && h->fused_mlp && h->crit_imgT && h->ttab.n > 0) {
+  if (bf_bwd && h->sw.fused_mlp && h->crit_imgT && h->ttab.n > 0) {
     MX(bf16_transposed_images(h->stream, h->bufs.crit_p, h->crit_imgT, h->ttab));
     h->imgT_ready = true;
   }

@@ -188,8 +188,8 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
       cur = q;
     }
     // ------------------------------------------------ L axis backward (per-sample [.,C] tiles, C = ik*id)
-    if (bf16 && fused_cube_bwd && !cfg.ln_first && pl <= 0.f && w.ax[0].res >= 0 && laxis_bwd_supported(il, hl, ol, ik * id) &&
-        (il <= 64 || laxis_bwd_long_on)) {   // (il > 64: the LONG instantiation, round 5b; MIMRL_LAXIS_BWD_LONG=0: the GEMM chain below)
+    if (bf16 && sw.fused_cube_bwd && !cfg.ln_first && pl <= 0.f && w.ax[0].res >= 0 && laxis_bwd_supported(il, hl, ol, ik * id) &&
+        (il <= 64 || sw.laxis_bwd_long)) {   // (il > 64: the LONG instantiation, round 5b; MIMRL_LAXIS_BWD_LONG=0: the GEMM chain below)
       // one launch: LayerNorm(L) backward -> dY -> dU -> dX (+ LayerNorm and bias gradients); weight gradients stay GEMMs
       const AxisW& a = w.ax[0];
       const long C = (long)ik * id;
@@ -315,20 +315,16 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
   return MIMRL_OK;
 }
 
-// Critical-path probe: with MIMRL_DBG_DELAY_TAG=<n> a single-wave kernel that spins MIMRL_DBG_DELAY_US (default 50)
-// microseconds is enqueued behind phase <n> on that phase's stream.  Step-time increase / injected time = how much of
+// Critical-path probe: with MIMRL_DBG_DELAY_TAG=<n>[:<us>] (Switches::dbg_delay_tag / _us) a single-wave kernel that spins <us>
+// (default 50) microseconds is enqueued behind phase <n> on that phase's stream.  Step-time increase / injected time = how much of
 // that phase sits on the critical path of the captured graph (tools/critical_path.sh); costs nothing when unset.
 __global__ void dbg_spin_kernel(long ticks) {
   const long t0 = wall_clock64();
   while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(16);
 }
 int mimrl_handle::dbg_delay(hipStream_t st, int tag) {
-  // MIMRL_DBG_DELAY_TAG=<tag>[:<microseconds>] (default 50 us)
-  static const char* spec = knob("MIMRL_DBG_DELAY_TAG");
-  static const int want = spec ? atoi(spec) : -1;
-  static const int us = spec && strchr(spec, ':') ? atoi(strchr(spec, ':') + 1) : 50;
-  if (tag != want) return MIMRL_OK;
-  hipLaunchKernelGGL(dbg_spin_kernel, dim3(1), dim3(64), 0, st, (long)us * 100);   // wall_clock64 ticks at 100 MHz
+  if (tag != sw.dbg_delay_tag) return MIMRL_OK;
+  hipLaunchKernelGGL(dbg_spin_kernel, dim3(1), dim3(64), 0, st, (long)sw.dbg_delay_us * 100);   // wall_clock64 ticks at 100 MHz
   LAUNCH_CHECK();
   return MIMRL_OK;
 }
@@ -410,7 +406,7 @@ int mimrl_handle::encoders_backward(float* dcube) {
       sd[m] = LnSide2{h1[m], P(ln_g[m]), P(ln_b[m]), ln_mean[m], ln_rstd[m], ds[m], Gm(ln_g[m]), Gm(ln_b[m]), 1 + m,
                       cfg.dropout[1 + m], (uint32_t)(1 + m)};
     // round 5b: ds as bf16 when the layer-1 BPTT launch can read it that way (GRU, bf16 BPTT with bf16 dg, 4-wave kernel)
-    ds_bf16_live = rec16_on && cfg.encoder == MIMRL_ENCODER_GRU && dg_bf16 && (prec & MIMRL_PREC_BF16_GRU_BWD) != 0 && gru_bwd_io16_ok(0);
+    ds_bf16_live = sw.rec16 && cfg.encoder == MIMRL_ENCODER_GRU && sw.dg_bf16 && (prec & MIMRL_PREC_BF16_GRU_BWD) != 0 && gru_bwd_io16_ok(0);
     MX(ln_relu_drop_bwd2(stream, sd[0], sd[1], dcube, B, T, L, 3, D, key(), dmean + (size_t)B * D, dmean + 2 * (size_t)B * D, ds_bf16_live ? 1 : 0));
   }
   // text branch (side 0): dW_t = dtx^T . text
@@ -457,7 +453,7 @@ int mimrl_handle::gru_layer_backward(int l) {
     a.stamp = kstamp; a.stamp.id = l == 1 ? 2 : 3;
     // layer 0 without packed inputs keeps fp32 dg: its dW_ih product reads the caller's unaligned [rows, 74 / 35] inputs through
     // the generic kernel, which has no bf16-operand variant
-    const bool lbf = dg_bf16 && (l == 1 || l0_packed || l0_bwd_pack);
+    const bool lbf = sw.dg_bf16 && (l == 1 || sw.l0_packed);
     a.dg_bf16 = lbf ? 1 : 0;
     a.slab_upl = l == 0 && l0_xin ? 2 : 0;   // the fused-projection forward wrote the 4-wave slab layout whatever MIMRL_GRU_WAVES says
     const bool io16 = lbf && (prec & MIMRL_PREC_BF16_GRU_BWD) != 0 && gru_bwd_io16_ok(a.slab_upl);
@@ -493,7 +489,7 @@ int mimrl_handle::gru_layer_backward(int l) {
         q.sb_b = gru[1][l][0].w_ih - gru[0][l][0].w_ih; q.sb2_b = gru[1][l][1].w_ih - gru[0][l][1].w_ih;
         q.sc_b = dh0[1] - dh0[0];
         if (lbf) { q.a_bf16 = 1; q.sa_b *= 2; q.sa2_b *= 2; }   // buffer distances are fp32-element counts; bf16 elements: x2
-        if (lbf && w1_img_valid && h16_on && w1b) {   // the weights from the bf16 image of this step's forward pass: half the B bytes
+        if (lbf && w1_img_valid && sw.h16 && w1b) {   // the weights from the bf16 image of this step's forward pass: half the B bytes
           q.B = reinterpret_cast<const float*>(w1b); q.B2 = reinterpret_cast<const float*>(w1b + (long)G * 2 * H);
           q.b_bf16 = 1; q.sb_b = 2L * G * 2 * H; q.sb2_b = 2L * G * 2 * H;
           // B * T >= 4096 rows: both operands k-contiguous -- the transposed image of the same bf16 values, the two
@@ -505,7 +501,7 @@ int mimrl_handle::gru_layer_backward(int l) {
             if (gemm_tall_ok(t)) {
               q = t;
               // round 5b: the tall kernel stores dh0 as bf16 when the layer-0 BPTT launch can read it that way (same element indices)
-              if (rec16_on && (prec & MIMRL_PREC_BF16_GRU_BWD) != 0 && (l0_packed || l0_bwd_pack) && gru_bwd_io16_ok(l0_xin ? 2 : 0)) { q.c_bf16 = 1; q.sc_b *= 2; dh0_bf16_live = true; }
+              if (sw.rec16 && (prec & MIMRL_PREC_BF16_GRU_BWD) != 0 && sw.l0_packed && gru_bwd_io16_ok(l0_xin ? 2 : 0)) { q.c_bf16 = 1; q.sc_b *= 2; dh0_bf16_live = true; }
             }
           }
         }
@@ -515,7 +511,7 @@ int mimrl_handle::gru_layer_backward(int l) {
     if (l == 1 && dbg_join_at == 3) MX(join(1, 3));
     // weight gradients of this layer: off the critical path.  Layer 1: side 1..3 (they overlap the layer-0 BPTT);
     // layer 0 is the tail of the stage.
-    if (l == 0 && (l0_packed || l0_bwd_pack)) {
+    if (l == 0 && sw.l0_packed) {
       // layer 0: the W_ih (against the packed inputs) and W_hh gradients of all four (modality, direction) pairs as two batched
       // launches into packed scratch, scattered into the bucket by one small kernel: 3 launches on 2 streams close the stage
       // instead of four GEMMs in a row (the per-modality widths 74 / 35 ruled out both batching and 16-byte loads)
@@ -523,9 +519,8 @@ int mimrl_handle::gru_layer_backward(int l) {
       const long s_hp = hprev[0][0][1] - hprev[0][0][0], o_hp = hprev[0][1][0] - hprev[0][0][0];
       // round 6: ONE pass over dg for both products of all four sequences (gru_wgrad.hip) when every operand is stored as bf16;
       // MIMRL_NO_GRU_WGRAD=1: the two batched split-K GEMMs below (each reads three of dg's four column blocks)
-      static const bool wgrad_on = knob("MIMRL_NO_GRU_WGRAD") == nullptr;   // tuning knob
       // (long sequences only: at cfg2's 6400 rows the launch is 40 us against 31 for the pair, whose two launches overlap -- 0.801 vs 0.799 ms)
-      const bool one_pass = wgrad_on && lbf && xpack16 && BT_ >= 32768 && gru_wgrad_ok(BT_, KP());
+      const bool one_pass = sw.gru_wgrad && lbf && xpack16 && BT_ >= 32768 && gru_wgrad_ok(BT_, KP());
       if (one_pass) {
         GruWgradArgs w;
         const __bf16* xb = reinterpret_cast<const __bf16*>(xpack + BT_ * KP());   // the bf16 copy of the packed inputs, [modality][B*T, KP]
@@ -579,7 +574,7 @@ int mimrl_handle::gru_layer_backward(int l) {
         // layer 1: the layer-0 outputs from the recurrence kernel's fp16 copy (half the bytes of an operand the 128-wide tiles fetch ~2x;
         // fp16 -> bf16 in registers: the product rounds to bf16 anyway, the double rounding moves a value by <= 2^-11 of itself).
         // MIMRL_DWIH_H16=0: the fp32 outputs.
-        if (lbf && both && dwih_h16_on && h16_live && h0h[0] && h0h[1]) {
+        if (lbf && both && sw.dwih_h16 && h16_live && h0h[0] && h0h[1]) {
           q.B = reinterpret_cast<const float*>(h0h[0]); q.b_bf16 = 1; q.b_f16cvt = 1; q.sb_bo = h0h[1] - h0h[0];
         }
         MX(G_on(pick(), q)); }

@@ -9,7 +9,7 @@
 int mimrl_handle::mlp_stack_forward(int nb, int rows, int brows, long p0, long pstride, int nl, const long (*l_off)[2],
                                     const int* dims, const float* in, float* const* act, float* out) {
   // (stacks with thousands of row tiles -- the unfused concat-critic tail -- take the GEMM chain: cfg3 9.80 vs 10.15 ms in round 2)
-  if (bf16 && fused_mlp && rows <= 512 && mlp_fused_supported(nb, rows, nl, dims)) {   // one launch (mlp_fused.hip)
+  if (bf16 && sw.fused_mlp && rows <= 512 && mlp_fused_supported(nb, rows, nl, dims)) {   // one launch (mlp_fused.hip)
     MlpFusedArgs fa;
     std::memset(&fa, 0, sizeof fa);
     fa.nb = nb; fa.rows = rows; fa.brows = brows; fa.nl = nl; fa.pstride = pstride; fa.in = in; fa.out = out;
@@ -42,9 +42,8 @@ int mimrl_handle::mlp_stack_backward(int nb, int rows, int brows, long p0, long 
   float* dz = dout;
   int pp = 0;
   // the fused data-gradient chain runs on the transposed bf16 images (the same coalesced loop as the forward pass)
-  static const bool fused_bwd = knob("MIMRL_NO_FUSED_MLP_BWD") == nullptr;
   // (stacks with thousands of row tiles -- the concat critic -- keep the GEMM chain here: measured faster than the fused one)
-  const bool use_fused = bf16 && fused_mlp && fused_bwd && imgT_ready && rows <= 512 && nl <= 4 && mlp_fused_supported(nb, rows, nl, dims);
+  const bool use_fused = bf16 && sw.fused_mlp && sw.fused_mlp_bwd && imgT_ready && rows <= 512 && nl <= 4 && mlp_fused_supported(nb, rows, nl, dims);
   // single-output top layer (the concat critic's score head) over many rows: one streaming kernel instead of three GEMMs with
   // one real column in 64 (dz, dW, both bias gradients)
   const bool top1 = !use_fused && dims[nl] == 1 && nl >= 2 && dims[nl - 1] % 4 == 0 && dims[nl - 1] <= 1024 && 1024 % dims[nl - 1] == 0 &&
@@ -179,10 +178,8 @@ int mimrl_handle::mi_forward(int stage, bool want_grad) {
   const int B = cfg.batch;
   const size_t BD = (size_t)B * EMB;
   const bool sep = cfg.critic_type == MIMRL_CRITIC_SEPARATE;
-  static const bool no_fused_mi = knob("MIMRL_NO_FUSED_MI") != nullptr;        // tuning knobs
-  static const bool no_nce_tiled = knob("MIMRL_NO_MI_NCE_TILED") != nullptr;
-  const bool fused_mi = sep && !no_fused_mi && bf16_fwd() && bf16_bwd() && mi_sep_fused_supported(B);
-  const bool nce_tiled = fused_mi && !no_nce_tiled && cfg.bound_type == MIMRL_BOUND_INFONCE && !has_baseline();
+  const bool fused_mi = sep && sw.fused_mi && bf16_fwd() && bf16_bwd() && mi_sep_fused_supported(B);
+  const bool nce_tiled = fused_mi && sw.mi_nce_tiled && cfg.bound_type == MIMRL_BOUND_INFONCE && !has_baseline();
   {   // tower inputs: x operand -> slot 2e, y operand -> slot 2e+1
     CopyTable t;
     t.n = 10;
@@ -233,7 +230,7 @@ int mimrl_handle::mi_forward(int stage, bool want_grad) {
     MX(G_(gq));
     // pair expansion + both hidden layers + score head in ONE launch with the activation tile in LDS (concat_fused.hip); the
     // unfused chain (fp32 mode, no bf16 image yet, MIMRL_NO_FUSED_CONCAT=1) is pair_expand + three GEMMs
-    if (fused_concat && bf16 && img_valid && crit_img && concat_fwd_fused_supported(B, HID)) {
+    if (sw.fused_concat && bf16 && img_valid && crit_img && concat_fwd_fused_supported(B, HID)) {
       ConcatFwdArgs fa;
       fa.P = cP; fa.Q = cQ;
       fa.W1 = crit_img + tower0 + tower_l[1][0]; fa.W2 = crit_img + tower0 + tower_l[2][0];
@@ -254,7 +251,7 @@ int mimrl_handle::mi_forward(int stage, bool want_grad) {
       // under which mi_backward routes there: concat_dw on, weights-stationary kernels with the in-kernel dQ reduction)
       {
         const long dq_need = concat_bwd_dq_scratch(NE_MI, B);
-        a0_regen_live = fa.save == 2 && knob("MIMRL_NO_CONCAT_DW") == nullptr && knob("MIMRL_NO_CONCAT_DQ") == nullptr &&
+        a0_regen_live = fa.save == 2 && sw.concat_dw && sw.concat_dq &&
                         concat_dw_ok(NE_MI, (long)B * B, HID) && concat_fwd_a2_f16(B, 2) && concat_bwd_ws_supported(B, HID) &&
                         dq_need > 0 && dq_need <= (long)NE_MI * B * B * HID;
         fa.no_a0 = a0_regen_live ? 1 : 0;
@@ -383,14 +380,12 @@ int mimrl_handle::mi_backward(int stage) {
     if (B > 128) HIPX(hipMemsetAsync(dP, 0, sizeof(float) * NE_MI * B * HID, stream));   // two or more tiles add into each dP row
     // dQ[j] = sum_i dZ0[i, j] inside the kernel (round 5: runs of tiles per workgroup, the partial sums in registers); before, dZ0 went
     // out in fp32 and pair_reduce_q read it back: 2 x 335 MB per pass at cfg3.  MIMRL_NO_CONCAT_DQ=1: that path
-    static const bool dq_knob = knob("MIMRL_NO_CONCAT_DQ") == nullptr;   // tuning knob
     const long dq_need = concat_bwd_dq_scratch(NE_MI, B);
-    const bool dq_in_kernel = dq_knob && dq_need > 0 && dq_need <= (long)NE_MI * B * B * HID;
+    const bool dq_in_kernel = sw.concat_dq && dq_need > 0 && dq_need <= (long)NE_MI * B * B * HID;
     if (dq_in_kernel) { fa.dQ = dQ; fa.dq_part = dca[2]; }   // (the partials live in the dz0 buffer they replace)
     // round 6b: the weights-stationary backward does not write dZ2 when the one-launch weight-gradient kernel will regenerate it
-    static const bool dw_on = knob("MIMRL_NO_CONCAT_DW") == nullptr;   // tuning knob
-    const bool use_dw = wgrad && dw_on && concat_dw_ok(NE_MI, (long)B * B, HID);
-    const bool dz2_regen = use_dw && dq_in_kernel && concat_bwd_ws_supported(B, HID) && !knob_on("MIMRL_CONCAT_STREAMED");
+    const bool use_dw = wgrad && sw.concat_dw && concat_dw_ok(NE_MI, (long)B * B, HID);
+    const bool dz2_regen = use_dw && concat_bwd_runs_ws(fa);   // (dq_in_kernel, and the dispatch of concat_bwd_fused below goes to concat_ws_bwd.hip)
     fa.no_dz2 = dz2_regen ? 1 : 0;
     if (wgrad && a0_regen_live && !dz2_regen) return set_error(MIMRL_ERR_STATE, "mi_backward: the forward pass did not save a0 but the one-launch weight-gradient kernel is off");
     MX(concat_bwd_fused(stream, fa));
@@ -518,7 +513,7 @@ int mimrl_handle::estimators_all(int stage, bool want_grad, bool backward) {
     frag_tr_deferred = false;
     return bf16_frag_images(st, bufs.crit_p, crit_frag, ftab_tr);
   };
-  if (backward && bf_bwd && fused_mlp && crit_imgT && ttab.n > 0) {   // transposed weight images for the fused data-gradient chains,
+  if (backward && bf_bwd && sw.fused_mlp && crit_imgT && ttab.n > 0) {   // transposed weight images for the fused data-gradient chains,
     if (!(skip_imgT_refresh && stage == 1)) {                         // built beside the forward stacks (combined step: once per step,
       MX(fork(3, 3));                                                 // in stage 2 -- stage 1 of the NEXT step sees the same critics)
       // capture order: the launch itself goes BEHIND the CMI branch's forward kernels (see cmi_branch) -- graph nodes are dispatched in

@@ -17,7 +17,7 @@ int mimrl_handle::encoders_forward(bool save, int knn_stage) {
   if (!ev_lens) MX(seq_lengths2(S(4), xin[0], dmod[0], lens[0], xin[1], dmod[1], lens[1], B, T));
   // 16-bit operands for the layer-1 projection (see h0h): bf16 recurrence + fp16 forward operands + the packed layer-0 launch that also
   // writes the weight images; a site forced to fp32 (MIMRL_FWD_FP32_SITES) or fp16-stored gx keeps the fp32-operand kernel
-  const bool use_h16 = h16_on && l0_packed && bf16 && fwd_f16 && (prec & MIMRL_PREC_BF16_GRU_FWD) && h0h[0] && w1h;
+  const bool use_h16 = sw.h16 && sw.l0_packed && bf16 && sw.fwd_f16 && (prec & MIMRL_PREC_BF16_GRU_FWD) && h0h[0] && w1h;
   // round 5b: with the fp16 copy feeding the layer-1 projection, dW_ih of layer 1 AND the layer-0 BPTT (h_prev), nobody reads the fp32 layer-0
   // outputs of a training pass any more -- the fused-projection forward then does not write them (262 MB per pass at cfg3).  The two flags
   // describe the pass whose activations the backward will read, i.e. they are recorded by SAVING passes only: in the non-shared prefetch mode
@@ -28,16 +28,10 @@ int mimrl_handle::encoders_forward(bool save, int knn_stage) {
     GruFwdArgs a;
     a.B = B; a.T = T; a.out_ld = 2 * H; a.nmod = 2;
     a.btv = gru_pick_btv(B, 2);
-    a.gx_f16 = gx_f16 ? 1 : 0;
+    a.gx_f16 = sw.gx_f16 ? 1 : 0;
     a.stamp = kstamp; a.stamp.id = l;
     if (l == 1) MX(fork(1, 3));
-    if (l == 0 && !l0_packed && l0_bwd_pack && save) {   // packed copy of the inputs for the layer-0 weight gradients: side 0 has slack
-      L0Pack pk;
-      for (int m = 0; m < 2; ++m) { pk.x[m] = xin[m]; pk.d[m] = dmod[m]; for (int d = 0; d < 2; ++d) { pk.w_ih[m][d] = nullptr; pk.b_ih[m][d] = nullptr; } }
-      pk.xpack = xpack; pk.wpack = wpack; pk.bpack = bpack; pk.rows = BT_; pk.KP = KP();
-      MX(l0_pack(S(0), pk, true, false));
-    }
-    if (l == 0 && l0_packed) {
+    if (l == 0 && sw.l0_packed) {
       // all four (modality, direction) projections of layer 0 as ONE batched launch on the packed operands
       L0Pack pk;
       for (int m = 0; m < 2; ++m) {
@@ -47,7 +41,7 @@ int mimrl_handle::encoders_forward(bool save, int knn_stage) {
       pk.xpack = xpack; pk.wpack = wpack; pk.bpack = bpack; pk.rows = BT_; pk.KP = KP();
       // ... and of the layer-0 projection itself: the pack launch writes its operands as fp16 (+ a bf16 copy of the inputs for the W_ih
       // weight gradient, whose other operand -- dg -- is bf16) INSTEAD of fp32, in the same buffers
-      const bool l0_16 = use_h16 && dg_bf16 && KP() % 8 == 0;
+      const bool l0_16 = use_h16 && sw.dg_bf16 && KP() % 8 == 0;
       xpack16 = l0_16;
       if (use_h16) {
         for (int m = 0; m < 2; ++m) for (int d = 0; d < 2; ++d) pk.w_ih1[m][d] = P(gru[m][1][d].w_ih);
@@ -68,17 +62,17 @@ int mimrl_handle::encoders_forward(bool save, int knn_stage) {
       gd.sa_b = 0; gd.sa_bo = BT_ * KP(); gd.sb_b = (long)G * KP(); gd.sb_bo = 2L * G * KP();
       gd.sc_b = gx[0][1] - gx[0][0]; gd.sc_bo = gx[1][0] - gx[0][0];
       gd.bias_n = bpack; gd.bias_n_b = G; gd.bias_n_bo = 2 * G;
-      gd.f16 = fwd_f16;
-      if (gx_f16) { gd.c_f16 = 1; gd.sc_b *= 2; gd.sc_bo *= 2; }   // buffer distances are fp32-element counts; fp16 elements: x2
+      gd.f16 = sw.fwd_f16;
+      if (sw.gx_f16) { gd.c_f16 = 1; gd.sc_b *= 2; gd.sc_bo *= 2; }   // buffer distances are fp32-element counts; fp16 elements: x2
       if (l0_16) { gd.a_bf16 = gd.b_bf16 = 1; }                    // (same element strides: the 16-bit arrays keep the fp32 ones' shapes)
       // Fused input projection (round 4): with the operands packed as fp16 the layer-0 recurrence kernel computes x W_ih^T + b_ih itself,
       // three k-steps per gate and cell step on a matrix pipe that is busy a quarter of the step: no GEMM launch, no gx round trip.
-      l0_xin = l0_16 && xin_on && KP() <= 96 && !gx_f16;
-      const bool hp16_now = use_h16 && rec16_on && save && dg_bf16 && (prec & MIMRL_PREC_BF16_GRU_BWD) != 0 && gru_bwd_io16_ok(l0_xin ? 2 : 0);
+      l0_xin = l0_16 && sw.xin && KP() <= 96 && !sw.gx_f16;
+      const bool hp16_now = use_h16 && sw.rec16 && save && sw.dg_bf16 && (prec & MIMRL_PREC_BF16_GRU_BWD) != 0 && gru_bwd_io16_ok(l0_xin ? 2 : 0);
       if (save) hp16_live = hp16_now;
       if (l0_xin) {
         a.xin_on = 1; a.kp = KP();
-        a.no_out32 = hp16_now && dwih_h16_on ? 1 : 0;   // every consumer of this pass's layer-0 outputs reads the fp16 copy
+        a.no_out32 = hp16_now && sw.dwih_h16 ? 1 : 0;   // every consumer of this pass's layer-0 outputs reads the fp16 copy
         for (int m = 0; m < 2; ++m) {
           a.xin[m] = pk.xh + (long)m * BT_ * KP();
           for (int d = 0; d < 2; ++d) { a.wih[m][d] = pk.wh + ((long)m * 2 + d) * G * KP(); a.bih[m][d] = bpack + ((long)m * 2 + d) * G; }
@@ -96,20 +90,20 @@ int mimrl_handle::encoders_forward(bool save, int knn_stage) {
       GemmDesc gd = gemm_nt(in, gf.din, P(gf.w_ih), gf.din, gx[m][0], G, (int)BT_, G, gf.din);
       gd.batch = 2; gd.sa_b = 0; gd.sb_b = gr.w_ih - gf.w_ih; gd.sc_b = gx[m][1] - gx[m][0];
       gd.bias_n = P(gf.b_ih); gd.bias_n_b = gr.b_ih - gf.b_ih;
-      gd.f16 = fwd_f16;
+      gd.f16 = sw.fwd_f16;
       if (l == 1) {
         gd.batch = 4; gd.batch_in = 2;
         gd.sa_bo = h0[1] - h0[0]; gd.sb_bo = gru[1][l][0].w_ih - gf.w_ih; gd.sc_bo = gx[1][0] - gx[0][0];
         gd.bias_n_bo = gru[1][l][0].b_ih - gf.b_ih;
       }
-      if (gx_f16) { gd.c_f16 = 1; gd.sc_b *= 2; gd.sc_bo *= 2; }
+      if (sw.gx_f16) { gd.c_f16 = 1; gd.sc_b *= 2; gd.sc_bo *= 2; }
       if (l == 1 && use_h16) {   // both operands as stored fp16 (strides in fp16 elements; the images are [modality][direction][G, 2H])
         gd.A = reinterpret_cast<const float*>(h0h[0]); gd.a_bf16 = 1; gd.sa_bo = h0h[1] - h0h[0];
         gd.B = reinterpret_cast<const float*>(w1h); gd.b_bf16 = 1; gd.sb_b = (long)G * 2 * H; gd.sb_bo = 2L * G * 2 * H;
       }
       // layer 1: the m == 0 launch covers both modalities; layer 0: video beside audio (side 2, or behind the length scan on side 4
       // when the overlap mode has masked side 2 off -- both are joined in front of the recurrence)
-      if ((l == 0 && !l0_packed) || (l == 1 && m == 0)) MX(G_on(m == 0 ? stream : (side_on(2) ? S(2) : S(4)), gd));
+      if ((l == 0 && !sw.l0_packed) || (l == 1 && m == 0)) MX(G_on(m == 0 ? stream : (side_on(2) ? S(2) : S(4)), gd));
       for (int d = 0; d < 2; ++d) {
         const GruDirW& g = gru[m][l][d];
         a.seq[m][d] = GruSeq{gx[m][d], P(g.w_hh), P(g.b_hh), l == 0 ? h0[m] : h1[m], save ? sv[l][m][d] : nullptr};
@@ -226,12 +220,12 @@ int mimrl_handle::model_forward(bool train, bool save, int knn_stage, int part) 
   const float pdrop[3] = {train ? cfg.dropout[0] : 0.f, train ? cfg.dropout[1] : 0.f, train ? cfg.dropout[2] : 0.f};
   // text_post + ln_relu_drop + feat_mean as one launch, one workgroup per (sample, slot): for short sequences, where the three
   // launches are latency (cfg2: -15 us per tail); a workgroup walking T = 1000 rows loses to the row-parallel kernels (cfg5: +60 us)
-  const bool fused_pre = fused_pre_on && T <= 128;
+  const bool fused_pre = sw.fused_pre && T <= 128;
   // ... and where block 0 of CubeMLP is the one-kernel form, that pass is its tile load (CubePre: no launch, no fp32 cube written and read back
   // unless the backward pass needs it); likewise the head is the last block's epilogue when its rows fit one LDS tile (CubeHead)
   const int nbl = cfg.n_blocks;
-  const bool fold_pre = cube_bookends && fused_pre && !pre_done && part != 1 && D == 128 && T <= L && cube_block_fused(0, train);
-  const bool fold_head = cube_bookends && part != 1 && cube_block_fused(nbl - 1, train) && cfg.d_outs[nbl - 1][0] * cfg.d_outs[nbl - 1][1] <= 64 &&
+  const bool fold_pre = sw.cube_bookends && fused_pre && !pre_done && part != 1 && D == 128 && T <= L && cube_block_fused(0, train);
+  const bool fold_head = sw.cube_bookends && part != 1 && cube_block_fused(nbl - 1, train) && cfg.d_outs[nbl - 1][0] * cfg.d_outs[nbl - 1][1] <= 64 &&
                          cfg.d_outs[nbl - 1][2] == 128;
   if (part != 1 && T < L && !pre_done && !fold_pre) HIPX(hipMemsetAsync(cube0, 0, sizeof(float) * (size_t)B * L * 3 * D, stream));
   if (part != 2) {
@@ -248,7 +242,7 @@ int mimrl_handle::model_forward(bool train, bool save, int knn_stage, int part) 
       MX(next_event(&ev_lens));
       HIPX(hipEventRecord(ev_lens, S(0)));
     }
-    { GemmDesc g = gemm_nt(bufs.text, cfg.d_t, P(w_t), cfg.d_t, tx_raw, D, (int)BT_, D, cfg.d_t); g.f16 = fwd_f16; MX(G_on(S(0), g)); }
+    { GemmDesc g = gemm_nt(bufs.text, cfg.d_t, P(w_t), cfg.d_t, tx_raw, D, (int)BT_, D, cfg.d_t); g.f16 = sw.fwd_f16; MX(G_on(S(0), g)); }
     MX(dbg_delay(S(0), 10));
     if (part == 0 && !fused_pre) MX(text_post_fwd(S(0), tx_raw, cube0, B, T, L, 3, D, 0, pdrop[0], key(), 0));
     MX(encoders_forward(save, knn_stage));
@@ -316,7 +310,7 @@ int mimrl_handle::dual_tail_pre() {
 
 // whether block i takes the one-kernel path of cube_forward below (the same test, on the same chain of block shapes)
 bool mimrl_handle::cube_block_fused(int i, bool train) const {
-  if (!bf16 || !fused_cube || i < 0 || i >= cfg.n_blocks) return false;
+  if (!bf16 || !sw.fused_cube || i < 0 || i >= cfg.n_blocks) return false;
   int il = cfg.time_len, ik = 3, id = cfg.d_common;
   for (int j = 0; j < i; ++j) { il = blk[j].ax[0].out; ik = blk[j].ax[1].out; id = blk[j].ax[2].out; }
   const BlockW& w = blk[i];
@@ -329,7 +323,7 @@ int mimrl_handle::cube_forward(bool train, bool save, const CubePre* pre, const 
   const int B = cfg.batch;
   const float* x = cube0;
   int il = cfg.time_len, ik = 3, id = cfg.d_common;
-  const bool no_fused = !fused_cube;
+  const bool no_fused = !sw.fused_cube;
   for (int i = 0; i < cfg.n_blocks; ++i) {
     const BlockW& w = blk[i];
     BlockBuf& b = bb[i];
@@ -375,7 +369,7 @@ int mimrl_handle::cube_forward(bool train, bool save, const CubePre* pre, const 
       const float* xi = x;
       // round 5b, long sequences (the fused block kernel above needs L <= 64): one pass over the [L, C] slab of every sample instead of two
       // GEMM launches that each read it, a padded-copy launch and the LayerNorm launch (cfg3: 275 -> ~80 us per forward tail)
-      const bool long_l = bf16 && laxis_long_on && !cfg.ln_first && pl <= 0.f && a.res >= 0 && laxis_fwd_long_supported(il, hl, ol, (int)C);
+      const bool long_l = bf16 && sw.laxis_long && !cfg.ln_first && pl <= 0.f && a.res >= 0 && laxis_fwd_long_supported(il, hl, ol, (int)C);
       if (long_l) {
         if (w2p[i] && hl % 4 != 0) {   // (the padded fc2 copy is still what the backward's dU product reads)
           MX(pad_rows(stream, P(a.fc2.w), w2p[i], ol, hl, (hl + 3) & ~3));
@@ -386,7 +380,7 @@ int mimrl_handle::cube_forward(bool train, bool save, const CubePre* pre, const 
         la.wr = P(a.res); la.g = P(a.ln_g); la.be = P(a.ln_b);
         la.u = b.l.u; la.h = b.l.h; la.y = b.l.y; la.z = b.l.z; la.mean = b.l.mean; la.rstd = b.l.rstd;
         la.B = B; la.il = il; la.hl = hl; la.ol = ol; la.C = (int)C; la.act = cfg.activation;
-        MX(laxis_fwd_long(stream, la, fwd_f16));
+        MX(laxis_fwd_long(stream, la, sw.fwd_f16));
       } else {
       if (cfg.ln_first) { MX(colln_fwd(stream, x, P(a.ln_g), P(a.ln_b), b.l.xn, b.l.xn_mean, b.l.xn_rstd, B, il, (int)C)); xi = b.l.xn; }
       GemmDesc g1;   // H = act(W1 . X_b + b1)
@@ -395,7 +389,7 @@ int mimrl_handle::cube_forward(bool train, bool save, const CubePre* pre, const 
       g1.C = b.l.h; g1.sc_m = C; g1.sc_n = 1; g1.sc_b = (long)hl * C;
       g1.M = hl; g1.N = (int)C; g1.K = il; g1.batch = B;
       g1.bias_m = a.fc1.b >= 0 ? P(a.fc1.b) : nullptr; g1.act = cfg.activation; g1.pre = b.l.u;
-      g1.f16 = fwd_f16;
+      g1.f16 = sw.fwd_f16;
       MX(G_(g1));
       GemmDesc g2;   // Y = W2 . H_b + b2
       g2.A = P(a.fc2.w); g2.sa_m = hl; g2.sa_k = 1;
@@ -486,7 +480,7 @@ int mimrl_handle::wt_images(hipStream_t st, bool bwd_bf16, bool launch, bool* d_
   ta.n = 0;
   for (int i = 0; i < cfg.n_blocks; ++i) {
     const AxisW& a = blk[i].ax[2];
-    d_fused[i] = bwd_bf16 && fused_cube_bwd && !cfg.ln_first && cfg.dropout_mlp[2] <= 0.f && a.res >= 0 &&
+    d_fused[i] = bwd_bf16 && sw.fused_cube_bwd && !cfg.ln_first && cfg.dropout_mlp[2] <= 0.f && a.res >= 0 &&
                  daxis_bwd_supported(din2, a.hid, a.out) && ta.n + 3 <= 12;
     din2 = cfg.d_outs[i][2];
     if (!d_fused[i]) continue;

@@ -10,14 +10,13 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
   const bool have_banks = bank_rows > 0;
   if (!keep_events) ev_next = 0;
   if (stage == 1) {
-    static const bool no_share = knob("MIMRL_NO_SHARED_PREFIX") != nullptr;   // tuning knob: evaluate the prefix twice
-    const bool share = prefetch && !no_share;
+    const bool share = prefetch && sw.shared_prefix;
     // counters + scalar reset: the first consumers are the kNN sampler and the recurrence.
     // shared-prefix step with packed layer-0 operands: the pack launch is the first kernel of the prefix on this stream and nothing in
     // front of the recurrence reads the counters or the scalars -- the bookkeeping rides on it (one launch + one gap less on the chain)
     // (first measured neutral, 0.970 vs 0.966 ms: the single-thread kernel hides in the gap between two graph launches;
     //  round 4, with the length scan on side 0: -4 us on average over four alternating runs, cfg3 neutral)
-    begin_in_pack = share && have_banks && skip_zero && l0_packed && cfg.encoder == MIMRL_ENCODER_GRU;
+    begin_in_pack = share && have_banks && skip_zero && sw.l0_packed && cfg.encoder == MIMRL_ENCODER_GRU;
     if (!begin_in_pack) {
       launch_begin_stage(stream, d_ints, have_banks ? d_ints + 2 : nullptr, bufs.scalars, 0, 32);
       LAUNCH_CHECK();
@@ -38,7 +37,7 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
         //     another captured stream sends this HIP runtime's EndCapture into an endless recursion.
         {
           Hold sides(side_mask, 0x11u);
-          MX(model_forward(true, true, knn_pre ? 3 : 1, 1));   // knn_pre: BOTH stages' samplers as one set of launches on side 4 (round 4)
+          MX(model_forward(true, true, 3, 1));   // BOTH stages' samplers as one set of launches on side 4 (round 4)
         }
         if (wtT_prebuilt) {   // combined step: the CubeMLP backward's weight images (main parameters only) on side 0 -- captured BEHIND the
           bool df[MIMRL_MAX_BLOCKS];   // encoders (nodes start in capture order: in front of them it delayed the input projections by 12 us);
@@ -49,8 +48,7 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
         // (stage 2's kNN sampler runs beside the prefix too -- the recurrence leaves half the CUs idle; its anchor key is the step counter
         //  begin_stage(2) will set: knn_launch(3))
         // (1b) long sequences: the pre-CubeMLP pieces of both tails in one launch (each source row read once)
-        static const bool dual_pre_on = knob("MIMRL_NO_DUAL_TAIL_PRE") == nullptr;   // tuning knob
-        const bool dual_pre = dual_pre_on && !defer_tail && cfg.seq_len > 128 && cfg.d_common == 128 && rng_add == 0;
+        const bool dual_pre = sw.dual_tail_pre && !defer_tail && cfg.seq_len > 128 && cfg.d_common == 128 && rng_add == 0;
         if (dual_pre) MX(dual_tail_pre());
         Hold pre(pre_done, dual_pre);   // both tails below skip those pieces
         hipEvent_t e_prefix = nullptr;
@@ -77,8 +75,8 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
         // behind one another (measured: with 5+ concurrent branches the step falls back to the sequential time, and the
         // prefetch chain as a separate graph on its own HIP stream is slower too), so stage 1's own forward pass keeps
         // two sides only
-        Hold sides(side_mask, 0x11u);        // text branch (side 0) + kNN sampler (side 4; knn_pre: stage 2's as well, one set of launches)
-        MX(model_forward(true, false, knn_pre ? 3 : 1));
+        Hold sides(side_mask, 0x11u);        // text branch (side 0) + kNN sampler (side 4; stage 2's as well, one set of launches)
+        MX(model_forward(true, false, 3));
       } else {
         MX(model_forward(true, false, 1));
       }
@@ -116,11 +114,7 @@ int mimrl_handle::enqueue_grads(int stage, bool skip_zero) {
   LAUNCH_CHECK();
   if (!skip_zero) HIPX(hipMemsetAsync(bufs.main_g, 0, sizeof(float) * layout.floats[MIMRL_GROUP_MAIN], stream));
   bf16 = bf16_fwd();
-  if (prefetch && have_banks) {   // forward pass (and kNN sampling) already done beside stage 1
-    if (!knn_pre) { MX(fork(4, 4)); MX(knn_launch(2, S(4))); MX(dbg_delay(S(4), 18)); }
-  } else {
-    MX(model_forward(true, true, have_banks ? 2 : 0));
-  }
+  if (!(prefetch && have_banks)) MX(model_forward(true, true, have_banks ? 2 : 0));   // (else: forward pass and kNN sampling already done beside stage 1)
   if (!fuse_boundary) {
     launch_task_loss(stream, task_loss, bufs.pred, bufs.labels, dpred, bufs.scalars + MIMRL_S2_TASK, B, ncls());
     LAUNCH_CHECK();
@@ -180,7 +174,7 @@ int mimrl_handle::enqueue_apply(int stage) {
   boundary_in_adam = false;
   const bool have_frag = stage == 1 && img_valid && crit_frag && ftab.n > 0;
   bool fwd_in_adam = false;
-  if (stage == 1 && fuse_boundary && adam_frag_on && a.n % 8 == 0) {
+  if (stage == 1 && fuse_boundary && sw.adam_frag && a.n % 8 == 0) {
     if (have_frag && a.n < (1L << 24)) {   // (the kernel's image index arithmetic is exact for buckets below 2^24 elements; larger: the frag_images launch)
       for (int e = 0; e < ftab.n && a.frag.n < 12; ++e)
         if (!ftab.tr[e] && ftab.dshift[e] == 0) {
@@ -259,9 +253,8 @@ int mimrl_handle::enqueue_grads2_reduced(bool skip_zero) {
 // Captured-graph diagnostics: MIMRL_GRAPH_DOT=<file> dumps the captured two-stage step (hipGraphDebugDotPrint: kernel names, edges).
 // (Rounds 4-5 also re-inserted fork edges here -- by height, captured-stream-first, pad nodes, a searched permutation: the captured order
 // was a local optimum of all of them; the machinery was removed in round 6, git keeps it.)
-static int graph_postprocess(hipGraph_t g) {
-  static const char* dot = knob("MIMRL_GRAPH_DOT");
-  if (dot) HIPX(hipGraphDebugDotPrint(g, dot, hipGraphDebugDotFlagsVerbose));
+static int graph_postprocess(hipGraph_t g, const std::string& dot) {
+  if (!dot.empty()) HIPX(hipGraphDebugDotPrint(g, dot.c_str(), hipGraphDebugDotFlagsVerbose));
   return MIMRL_OK;
 }
 
@@ -282,7 +275,7 @@ int mimrl_handle::replay_or_capture(CachedGraph& slot, Body&& body, bool postpro
     const hipError_t ce = hipStreamEndCapture(cap_stream, &g);
     if (r != 0) { if (g) (void)hipGraphDestroy(g); return r; }
     if (ce != hipSuccess) return set_error(MIMRL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-    if (postprocess) { const int pr = graph_postprocess(g); if (pr != 0) { (void)hipGraphDestroy(g); return pr; } }
+    if (postprocess) { const int pr = graph_postprocess(g, sw.graph_dot); if (pr != 0) { (void)hipGraphDestroy(g); return pr; } }
     const hipError_t ie = hipGraphInstantiate(&slot.exec, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
     if (ie != hipSuccess) { slot.exec = nullptr; return set_error(MIMRL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie)); }
@@ -332,7 +325,7 @@ int mimrl_handle::run(int stage, int kind) {
     }
     {
       Hold part(split_part, kind == 3 ? 1 : 0);
-      Hold fold(fold_unpack, kind == 0 && stage == 2 && fold_unpack_on);   // the update follows in the same enqueue: it scatters the packed layer-0 pieces
+      Hold fold(fold_unpack, kind == 0 && stage == 2 && sw.fold_unpack);   // the update follows in the same enqueue: it scatters the packed layer-0 pieces
       const int r = enqueue_grads(stage, skip_zero);
       if (r != 0) unpack_pending = false;
       MX(r);
@@ -478,12 +471,11 @@ int mimrl_handle::run_step() {
   Range rg("mimrl.two_stage_step (Solver.step)");
   if (!bound) return set_error(MIMRL_ERR_STATE, "mimrl_bind must be called before any step");
   pipe_primed = false; knn_flip = 0;
-  static const bool no_step_graph = knob("MIMRL_NO_STEP_GRAPH") != nullptr;   // tuning knob
-  const bool combined = cfg.use_graph && !prof_on && prefetch && !defer_tail && bank_rows > 0 && grads_clean[1] && grads_clean[2] && !no_step_graph;
+  const bool combined = cfg.use_graph && !prof_on && prefetch && !defer_tail && bank_rows > 0 && grads_clean[1] && grads_clean[2] && sw.step_graph;
   if (!combined) { MX(run(1, 0)); if (defer_tail) MX(run_fwd2_tail()); return run(2, 0); }
   MX(ensure_images());
   const bool bf_bwd = bf16_bwd();
-  const bool use_imgT = bf_bwd && fused_mlp && crit_imgT && ttab.n > 0;
+  const bool use_imgT = bf_bwd && sw.fused_mlp && crit_imgT && ttab.n > 0;
   if (use_imgT && !imgT_valid) {   // the captured stage 1 relies on the images left by the previous step's stage 2
     MX(bf16_transposed_images(user_stream, bufs.crit_p, crit_imgT, ttab));
     imgT_valid = true;
@@ -492,7 +484,7 @@ int mimrl_handle::run_step() {
     // capture-only state (engine.h); wtT_built is read only while wtT_prebuilt holds, so what it goes back to is never seen
     Hold boundary(fuse_boundary, true);
     Hold images_current(skip_imgT_refresh, use_imgT);
-    Hold prebuilt(wtT_prebuilt, bf_bwd && fused_cube_bwd);
+    Hold prebuilt(wtT_prebuilt, bf_bwd && sw.fused_cube_bwd);
     Hold built(wtT_built, false);
     Hold scatter_owed(unpack_pending, false);  // (false between calls; put back on a failure between the stage-2 gradients and their update)
     MX(enqueue_grads(1, true));
@@ -500,7 +492,7 @@ int mimrl_handle::run_step() {
     MX(enqueue_apply(1));
     {
       Hold reserved(keep_events, true);
-      Hold fold(fold_unpack, fold_unpack_on && !comm);   // (data parallel: the packed layer-0 pieces must be IN the bucket before it is reduced)
+      Hold fold(fold_unpack, sw.fold_unpack && !comm);   // (data parallel: the packed layer-0 pieces must be IN the bucket before it is reduced)
       if (comm && comm_split && cfg.encoder == MIMRL_ENCODER_GRU) MX(enqueue_grads2_reduced(true));
       else { MX(enqueue_grads(2, true)); MX(reduce_bucket(2)); }
     }

@@ -1,5 +1,5 @@
-"""Worker of tests/test_gpu_step.py::test_every_registered_knob_vs_oracle: ONE process with ONE environment knob set (the library reads most
-knobs once per process), the benchmarked bf16 mode on two fixtures (`tiny_sep`: separable critics, T = 6; `cfg1_cat`: BASELINE configs[0]'s
+"""Worker of tests/test_gpu_step.py::test_every_registered_knob_vs_oracle: ONE process with ONE environment knob set (the engine reads its
+knobs once per handle; gru.hip, gemm_tall.hip, lstm.hip, mlp_fused.hip and concat_fused.hip read theirs once per process or per call), the benchmarked bf16 mode on two fixtures (`tiny_sep`: separable critics, T = 6; `cfg1_cat`: BASELINE configs[0]'s
 shape with the concat critic).  For both stages: stage loss and MI / CMI values against the oracle's autograd (oracle/mimrl_ref.py, pinned to
 the reference by tests/golden), gradient buckets by cosine against the oracle, every gradient tensor dumped for the parent (which compares
 it with the default-knob run), then two captured-graph steps in Solver.step() overlap mode that must stay finite."""

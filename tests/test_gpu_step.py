@@ -258,18 +258,13 @@ def test_stage2_prefetch_matches_sequential(precision, use_graph, split):
     _prefetch_matches_sequential(precision, use_graph, split)
 
 
-def test_prefetch_without_the_shared_prefix_matches_sequential():
+def test_prefetch_without_the_shared_prefix_matches_sequential(monkeypatch):
     """MIMRL_NO_SHARED_PREFIX=1 (a tuning knob: both forward passes evaluate the encoders): stage 1's own, NON-saving forward pass is captured
     behind the saving stage-2 pass, so per-pass facts the backward relies on -- which 16-bit copies the saving pass wrote, whether it wrote its
-    fp32 layer-0 outputs at all (round 5b: MIMRL_REC16) -- must be those of the SAVING pass.  The knob is read once per process: the overlap
-    parity cases run again in a child process with it set."""
-    import subprocess
-    import sys
-    env = dict(os.environ, MIMRL_NO_SHARED_PREFIX="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-m", "gpu", "-x", "-p", "no:cacheprovider",
-                        "-k", "test_stage2_prefetch_matches_sequential and bf16"], env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert " passed" in r.stdout and "failed" not in r.stdout, r.stdout[-1000:]
+    fp32 layer-0 outputs at all (round 5b: MIMRL_REC16) -- must be those of the SAVING pass.  The engine reads the knob when a handle is
+    created: the bf16 overlap parity case runs again with it set."""
+    monkeypatch.setenv("MIMRL_NO_SHARED_PREFIX", "1")
+    _prefetch_matches_sequential("bf16", True, False)
 
 
 def _prefetch_matches_sequential(precision, use_graph, split):
@@ -925,6 +920,44 @@ def test_critic_update_with_fragment_images_and_stage_boundary_changes_nothing(w
         assert np.isfinite(pa).all() and np.abs(pa - b[1][n]).max() <= 2 * 2 * 4e-3 + 1e-6, n      # (at most two sign-like Adam steps apart)
 
 
+@pytest.mark.parametrize("order", ["per_stage_first", "combined_first"])
+def test_engine_knobs_are_per_handle(order, monkeypatch, tmp_path):
+    """Every engine knob is read when a handle is created (csrc/engine.h: Switches), none frozen at first use for the process: of two engines
+    created one after the other in THIS process, the one created under MIMRL_NO_STEP_GRAPH=1 never captures the combined two-stage graph --
+    only that capture dumps MIMRL_GRAPH_DOT -- and the one created without it does, into the file named at ITS creation; in either order."""
+    dot = {"A": tmp_path / "a.dot", "B": tmp_path / "b.dot"}
+
+    def two_steps(tag):
+        if tag == "A":
+            monkeypatch.setenv("MIMRL_NO_STEP_GRAPH", "1")
+        else:
+            monkeypatch.delenv("MIMRL_NO_STEP_GRAPH", raising=False)
+        monkeypatch.setenv("MIMRL_GRAPH_DOT", str(dot[tag]))
+        c, opt, batch, banks, p, eng = make_engine("tiny_sep", precision="bf16", use_graph=True)
+        anchors = load_golden("tiny_sep")["anchors"][0]
+        eng.set_banks(*(banks[k] for k in "CFTAV"))
+        eng.set_stage2_prefetch(1)
+        eng.set_anchors(1, anchors[0]); eng.set_anchors(2, anchors[1])
+        for _ in range(2):
+            eng.step()
+        torch.cuda.synchronize()
+        assert np.isfinite(eng.read_scalars()).all() and torch.isfinite(eng.main["p"]).all() and torch.isfinite(eng.crit["p"]).all(), tag
+        eng.close()
+
+    if order == "per_stage_first":
+        two_steps("A")
+        assert not dot["A"].exists()
+        two_steps("B")
+        assert dot["B"].stat().st_size > 1000
+        assert not dot["A"].exists()
+    else:
+        two_steps("B")
+        assert dot["B"].stat().st_size > 1000
+        dot["B"].unlink()
+        two_steps("A")
+        assert not dot["A"].exists() and not dot["B"].exists()
+
+
 def _registered_knobs():
     """(name, help) of every row of csrc/knobs.cpp's table -- the one list of environment knobs the native library reads."""
     import re
@@ -944,7 +977,8 @@ def _knob_value(knob, help_):
 
 def _knob_run(tmp_path_factory, knob, value):
     """Result of the worker under (knob, value).  The FIRST call runs the whole table (and the default run) four processes at a time -- one
-    process per knob because the library reads most of them once per process -- and caches it: ~40 x 10 s of mostly host time."""
+    process per knob because gru.hip, gemm_tall.hip, lstm.hip, mlp_fused.hip and concat_fused.hip read theirs once per process or per call (the
+    engine's own are read per handle) -- and caches it: ~40 x 10 s of mostly host time."""
     if not _KNOB_RUNS:
         from concurrent.futures import ThreadPoolExecutor
         root = tmp_path_factory.mktemp("knobs")
