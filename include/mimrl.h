@@ -387,6 +387,29 @@ int mimrl_probe_cmi(mimrl_handle* h, int stage, const float* cmi_in, float* logi
 int mimrl_probe_knn(mimrl_handle* h, int stage, int32_t* idx_out);
 int mimrl_op_adam(void* stream, float* p, float* g, float* m, float* v, int64_t n, const float* lr, const int32_t* step,
                   float beta1, float beta2, float eps, float weight_decay, float clip);
+/* The same launch in the full form the engine's update uses (test-facing).  The gradient is g (+ the parked pieces) * gscale; pimg (bf16 [n]
+ * or NULL) receives the bf16 image of the updated parameters.
+ * Parked pieces (nfold <= 8, HOST arrays of nfold entries): bucket elements [fold_lo[q], fold_lo[q] + fold_rows[q] * fold_d[q]) also take
+ * fold_src[q][row * fold_ld[q] + col] (device float [fold_rows[q]][fold_ld[q]], fold_ld[q] >= fold_d[q]), and the launch leaves the whole of
+ * fold_src[q] zero, padding columns included.
+ * Fragment images (nfrag <= 12, HOST arrays of nfrag entries; needs n % 8 == 0, n < 2^24 and nfold == 0: the 8-wide kernel): entry e is
+ * frag_nb[e] row-major matrices [frag_OUT[e]][frag_RED[e]] at frag_off[e] + i * frag_gstride[e]; frag_dst (bf16 [n]) receives their
+ * fragment-order images as mimrl_op_frag_images writes them with tr = 0, dshift = 0, positions outside the matrices stay untouched.
+ * Everything the launch cannot do is refused before it. */
+int mimrl_op_adam_ex(void* stream, float* p, float* g, float* m, float* v, int64_t n, const float* lr, const int32_t* step,
+                     float beta1, float beta2, float eps, float weight_decay, float clip, float gscale, void* pimg,
+                     int nfold, const int64_t* fold_lo, const int32_t* fold_rows, const int32_t* fold_d, const int32_t* fold_ld,
+                     float* const* fold_src,
+                     int nfrag, const int64_t* frag_off, const int32_t* frag_OUT, const int32_t* frag_RED, const int32_t* frag_nb,
+                     const int64_t* frag_gstride, void* frag_dst);
+/* Fragment-order bf16 images of a table of n (1..24; HOST arrays) strided groups of matrices of the fp32 buffer src (test-facing; the images
+ * the fused estimator stacks read their weights from).  Entry e: nb[e] matrices at base = off[e] + i * gstride[e] with OUT[e] (a multiple of
+ * 32) columns c and a reduction length RED[e] (a multiple of 64) of rows r; element (c, r) = src[base + c * RED + r] (tr[e] = 0) or
+ * src[base + r * OUT + c] (tr[e] = 1);
+ *   dst[dshift[e] + base + ((c / 32 * (RED / 16) + r / 16) * 64 + c % 32 + 32 * ((r % 16) / 8)) * 8 + r % 8] = bf16(element (c, r)).
+ * off, gstride and dshift are multiples of 8; nothing else of dst is written.  The caller sizes src and dst. */
+int mimrl_op_frag_images(void* stream, const float* src, void* dst, int n, const int64_t* off, const int32_t* OUT, const int32_t* RED,
+                         const int32_t* nb, const int32_t* tr, const int64_t* gstride, const int64_t* dshift);
 
 #ifdef __cplusplus
 }

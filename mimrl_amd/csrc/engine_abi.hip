@@ -824,4 +824,62 @@ int mimrl_op_adam(void* stream, float* p, float* g, float* m, float* v, int64_t 
   return adam_step(reinterpret_cast<hipStream_t>(stream), a);
 }
 
+int mimrl_op_adam_ex(void* stream, float* p, float* g, float* m, float* v, int64_t n, const float* lr, const int32_t* step,
+                     float beta1, float beta2, float eps, float weight_decay, float clip, float gscale, void* pimg,
+                     int nfold, const int64_t* fold_lo, const int32_t* fold_rows, const int32_t* fold_d, const int32_t* fold_ld,
+                     float* const* fold_src,
+                     int nfrag, const int64_t* frag_off, const int32_t* frag_OUT, const int32_t* frag_RED, const int32_t* frag_nb,
+                     const int64_t* frag_gstride, void* frag_dst) {
+  if (!p || !g || !m || !v || !lr || !step || n < 1) return set_error(MIMRL_ERR_ARG, "mimrl_op_adam_ex: null array or n < 1");
+  AdamArgs a;
+  a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.lr = lr; a.step = step;
+  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.clip = clip;
+  a.gscale = gscale; a.pimg = static_cast<__bf16*>(pimg);
+  if (nfold < 0 || nfold > 8) return set_error(MIMRL_ERR_ARG, "mimrl_op_adam_ex: %d parked pieces outside [0, 8]", nfold);
+  if (nfold > 0 && (!fold_lo || !fold_rows || !fold_d || !fold_ld || !fold_src)) return set_error(MIMRL_ERR_ARG, "mimrl_op_adam_ex: null fold array");
+  for (int q = 0; q < nfold; ++q) {
+    if (!fold_src[q] || fold_rows[q] < 1 || fold_d[q] < 1 || fold_ld[q] < fold_d[q] || fold_lo[q] < 0 ||
+        fold_lo[q] + (int64_t)fold_rows[q] * fold_d[q] > n)
+      return set_error(MIMRL_ERR_ARG, "mimrl_op_adam_ex: parked piece %d is not rows x d <= ld inside the bucket", q);
+    a.fold.lo[q] = fold_lo[q]; a.fold.hi[q] = fold_lo[q] + (long)fold_rows[q] * fold_d[q];
+    a.fold.src[q] = fold_src[q]; a.fold.d[q] = fold_d[q]; a.fold.ld[q] = fold_ld[q];
+  }
+  a.fold.n = nfold;
+  if (nfold > 0) {
+    a.fold.lo_all = a.fold.lo[0]; a.fold.hi_all = a.fold.hi[0];
+    for (int q = 1; q < a.fold.n; ++q) { a.fold.lo_all = std::min(a.fold.lo_all, a.fold.lo[q]); a.fold.hi_all = std::max(a.fold.hi_all, a.fold.hi[q]); }
+  }
+  if (nfrag < 0 || nfrag > 24) return set_error(MIMRL_ERR_ARG, "mimrl_op_adam_ex: %d image entries outside [0, 24]", nfrag);
+  if (nfrag > 0) {
+    if (!frag_off || !frag_OUT || !frag_RED || !frag_nb || !frag_gstride || !frag_dst) return set_error(MIMRL_ERR_ARG, "mimrl_op_adam_ex: null image array");
+    FragTable t;
+    std::memset(&t, 0, sizeof t);
+    t.n = nfrag;
+    for (int e = 0; e < nfrag; ++e) {
+      const int64_t mat = (int64_t)frag_OUT[e] * frag_RED[e];
+      if (frag_OUT[e] < 32 || frag_OUT[e] % 32 != 0 || frag_RED[e] < 64 || frag_RED[e] % 64 != 0 || frag_nb[e] < 1 || frag_off[e] < 0 ||
+          frag_off[e] % 8 != 0 || frag_gstride[e] % 8 != 0 || frag_gstride[e] < mat || frag_off[e] + (frag_nb[e] - 1) * frag_gstride[e] + mat > n)
+        return set_error(MIMRL_ERR_ARG, "mimrl_op_adam_ex: image entry %d is not nb x [32k x 64k] at 16-byte offsets inside the bucket", e);
+      t.off[e] = frag_off[e]; t.OUT[e] = frag_OUT[e]; t.RED[e] = frag_RED[e]; t.nb[e] = frag_nb[e]; t.gstride[e] = frag_gstride[e];
+    }
+    if (!adam_frag_from_table(a, t, static_cast<__bf16*>(frag_dst))) return set_error(MIMRL_ERR_ARG, "mimrl_op_adam_ex: more than 12 image entries");
+  }
+  return adam_step(reinterpret_cast<hipStream_t>(stream), a);
+}
+
+int mimrl_op_frag_images(void* stream, const float* src, void* dst, int n, const int64_t* off, const int32_t* OUT, const int32_t* RED,
+                         const int32_t* nb, const int32_t* tr, const int64_t* gstride, const int64_t* dshift) {
+  if (!src || !dst || !off || !OUT || !RED || !nb || !tr || !gstride || !dshift) return set_error(MIMRL_ERR_ARG, "mimrl_op_frag_images: null argument");
+  if (n < 1 || n > 24) return set_error(MIMRL_ERR_ARG, "mimrl_op_frag_images: %d table entries outside [1, 24]", n);
+  FragTable t;
+  std::memset(&t, 0, sizeof t);
+  t.n = n;
+  for (int e = 0; e < n; ++e) {
+    if (OUT[e] < 32 || RED[e] < 64 || nb[e] < 1 || off[e] < 0 || off[e] + dshift[e] < 0 || gstride[e] < (int64_t)OUT[e] * RED[e])
+      return set_error(MIMRL_ERR_ARG, "mimrl_op_frag_images: entry %d has an empty matrix, a negative offset or overlapping groups", e);
+    t.off[e] = off[e]; t.OUT[e] = OUT[e]; t.RED[e] = RED[e]; t.nb[e] = nb[e]; t.tr[e] = tr[e] != 0; t.gstride[e] = gstride[e]; t.dshift[e] = dshift[e];
+  }
+  return bf16_frag_images(reinterpret_cast<hipStream_t>(stream), src, static_cast<__bf16*>(dst), t);
+}
+
 }  // extern "C"

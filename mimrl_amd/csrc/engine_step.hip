@@ -176,16 +176,7 @@ int mimrl_handle::enqueue_apply(int stage) {
   bool fwd_in_adam = false;
   if (stage == 1 && fuse_boundary && sw.adam_frag && a.n % 8 == 0) {
     if (have_frag && a.n < (1L << 24)) {   // (the kernel's image index arithmetic is exact for buckets below 2^24 elements; larger: the frag_images launch)
-      for (int e = 0; e < ftab.n && a.frag.n < 12; ++e)
-        if (!ftab.tr[e] && ftab.dshift[e] == 0) {
-          const int q = a.frag.n++;
-          a.frag.lo[q] = ftab.off[e]; a.frag.gstride[q] = ftab.gstride[e]; a.frag.nb[q] = ftab.nb[e];
-          a.frag.mat[q] = ftab.OUT[e] * ftab.RED[e]; a.frag.RED[q] = ftab.RED[e];
-          a.frag.inv_gs[q] = 1.f / (float)ftab.gstride[e]; a.frag.inv_red[q] = 1.f / (float)ftab.RED[e];
-        }
-      int nfwd = 0;
-      for (int e = 0; e < ftab.n; ++e) nfwd += !ftab.tr[e];
-      if (a.frag.n == nfwd) { a.frag.dst = crit_frag; fwd_in_adam = true; } else a.frag.n = 0;
+      fwd_in_adam = adam_frag_from_table(a, ftab, crit_frag);
     }
     a.sb_on = 1;
     a.sb = StageBoundaryArgs{bufs.scalars, mi_raw, cmi_raw, bce_raw, coef1(), d_ints, d_ints + 1, bufs.pred, bufs.labels, dpred, cfg.batch, ncls()};

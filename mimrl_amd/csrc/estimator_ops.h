@@ -117,6 +117,11 @@ struct AdamArgs {
 };
 // sb_kind: the task loss of the stage boundary when a.sb_on (MIMRL_TASK_LOSS_*), chooses the adam8_kernel instantiation
 int adam_step(hipStream_t s, const AdamArgs& a, int sb_kind = MIMRL_TASK_LOSS_MAE);
+// a.frag from the FORWARD entries (tr = 0, no dshift) of a fragment-image table, with the reciprocals adam8_kernel's index arithmetic uses
+// (host only; enqueue_apply and mimrl_op_adam_ex).  true: every forward entry of t is in a.frag and a.frag.dst = dst; false (more than 12
+// of them, or one with a dshift): a.frag is left empty.
+struct FragTable;
+bool adam_frag_from_table(AdamArgs& a, const FragTable& t, __bf16* dst);
 
 #ifdef MIMRL_PHASE_PROBE
 int nce_read_phases(long long* out);   // 8 ticks, see estimator_ops.hip

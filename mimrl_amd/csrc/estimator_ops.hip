@@ -1,5 +1,6 @@
 // Estimator-side kernels (see estimator_ops.h for reference citations).
 #include "estimator_ops.h"
+#include "mlp_fused.h"
 
 namespace mimrl {
 
@@ -968,6 +969,22 @@ int top1_bwd(hipStream_t s, const float* dout, const float* W, const float* act,
                      pstride);
   LAUNCH_CHECK();
   return MIMRL_OK;
+}
+
+bool adam_frag_from_table(AdamArgs& a, const FragTable& t, __bf16* dst) {
+  a.frag.n = 0;
+  for (int e = 0; e < t.n && a.frag.n < 12; ++e)
+    if (!t.tr[e] && t.dshift[e] == 0) {
+      const int q = a.frag.n++;
+      a.frag.lo[q] = t.off[e]; a.frag.gstride[q] = t.gstride[e]; a.frag.nb[q] = t.nb[e];
+      a.frag.mat[q] = t.OUT[e] * t.RED[e]; a.frag.RED[q] = t.RED[e];
+      a.frag.inv_gs[q] = 1.f / (float)t.gstride[e]; a.frag.inv_red[q] = 1.f / (float)t.RED[e];
+    }
+  int nfwd = 0;
+  for (int e = 0; e < t.n; ++e) nfwd += !t.tr[e];
+  if (a.frag.n != nfwd) { a.frag.n = 0; return false; }
+  a.frag.dst = dst;
+  return true;
 }
 
 int adam_step(hipStream_t s, const AdamArgs& a, int sb_kind) {
