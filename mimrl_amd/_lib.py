@@ -23,7 +23,11 @@ PHASES = ["gemm_misc", "gru_fwd", "gru_bwd", "cube_fwd", "cube_bwd", "est_fwd", 
 S1_LOSS, S1_MIS, S1_LOSSES, S2_LOSS, S2_TASK, S2_MIS, S2_LOSSES = 0, 1, 12, 32, 33, 34, 42
 
 BOUNDS = {"infonce": 0, "nwj": 1, "tuba": 2, "dv": 3, "js_fgan": 4, "js": 5, "smile": 6, "mine": 7, "interpolate": 8}
-ACTS = {"none": 0, "relu": 1, "gelu": 2, "tanh": 3}
+ACTS = {"none": 0, "relu": 1, "gelu": 2, "tanh": 3, "elu": 4, "leakyrelu": 5, "hardtanh": 6}      # MIMRL_ACT_*
+# the rest of the reference's table (Utils.py:84-97) and why CubeMLP does not run them
+ACTS_REFUSED = {"prelu": "it has a learnable slope, which the parameter layout does not hold",
+                "rrelu": "it draws random slopes in training mode, which the backward pass would have to save per element",
+                "hardshrink": "there is no oracle to hold it to yet"}
 # (the two GRU bits go together: the forward kernel writes the gate slab in the format the BPTT kernel of the same mode reads)
 PREC = {"fp32": 0, "bf16": 15, "bf16_gemm_fwd": 1, "bf16_gemm_bwd": 2, "bf16_gemm": 3, "bf16_gru": 12, "bf16_nogemmbwd": 13}
 
@@ -254,7 +258,9 @@ def make_cfg(opt, d_t: int, d_a: int, d_v: int, seq_len: int = None, bank_capaci
         c.res_project[i] = int(bool(opt.res_project[i]))
     c.bias, c.ln_first = int(bool(opt.bias)), int(bool(opt.ln_first))
     if opt.activate not in ACTS:
-        raise MimrlError(f"--activate {opt.activate} not supported on the HIP path (gelu/relu/tanh)")
+        why = ACTS_REFUSED.get(opt.activate)
+        raise MimrlError(f"--activate {opt.activate} not supported on the HIP path" + (f": {why}" if why else "") +
+                         f" (choose one of {', '.join(a for a in ACTS if a != 'none')})")
     c.activation = ACTS[opt.activate]
     for name, attr in (("features_compose_t", "compose_t_sum"), ("features_compose_k", "compose_k_sum")):
         v = getattr(opt, name, "mean")

@@ -69,7 +69,7 @@ extern const char* const kDebugKnobs[];
 // ----------------------------------------------------------------------------------------------
 // device math
 // ----------------------------------------------------------------------------------------------
-enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_TANH = 3 };
+enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_TANH = 3, ACT_ELU = 4, ACT_LEAKYRELU = 5, ACT_HARDTANH = 6 };
 
 // erf via Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. fp32 noise) on v_exp/v_rcp: ~15 instructions instead of
 // libm erff's ~60 -- the exact-erf GELU (F.gelu default, MLPProcess.py:14 / Utils.py:86) is the dominant VALU cost
@@ -92,11 +92,18 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
   const float erfv = copysignf(1.0f - poly * ex, x);
   return 0.5f * (1.0f + erfv) + x * (0.39894228040143267794f * ex);
 }
+// elu (alpha = 1), leakyrelu (slope 0.01), hardtanh ([-1, 1]): the defaults of nn.ELU(), nn.LeakyReLU(), nn.Hardtanh() (Utils.py:84-97).
+// Branch-free over the positive part max(x, 0) and the negative part min(x, 0): these cases are inlined into every unrolled iteration of the
+// kernels' generic copy, where a `x > 0 ? x : ...` becomes an exec-mask branch per element.  elu's exp(x) - 1 on v_exp_f32: absolute error
+// ~1e-7 (fp32 noise, like fast_erf), exactly 0 at 0; libm's expm1f is not worth its size here
 __device__ __forceinline__ float act_apply(int act, float x) {
   switch (act) {
     case ACT_RELU: return x > 0.f ? x : 0.f;
     case ACT_GELU: return gelu_f(x);
     case ACT_TANH: return tanhf(x);
+    case ACT_ELU: return fmaxf(x, 0.f) + (__expf(fminf(x, 0.f)) - 1.f);
+    case ACT_LEAKYRELU: return fmaxf(x, 0.f) + 0.01f * fminf(x, 0.f);
+    case ACT_HARDTANH: return fminf(fmaxf(x, -1.f), 1.f);
     default: return x;
   }
 }
@@ -106,11 +113,14 @@ __device__ __forceinline__ float act_grad(int act, float u) {
     case ACT_RELU: return u > 0.f ? 1.f : 0.f;
     case ACT_GELU: return gelu_grad_f(u);
     case ACT_TANH: { float t = tanhf(u); return 1.f - t * t; }
+    case ACT_ELU: return __expf(fminf(u, 0.f));                           // 1 for u >= 0
+    case ACT_LEAKYRELU: return u > 0.f ? 1.f : 0.01f;
+    case ACT_HARDTANH: return fabsf(u) < 1.f ? 1.f : 0.f;               // the clamp passes no gradient AT its bounds either
     default: return 1.f;
   }
 }
 // Activation known at compile time (ACT >= 0) or not (ACT < 0: the run-time switch).  Round 3b: an epilogue that calls act_apply(act, u) per
-// element carries the whole switch -- three activations, ~13 scalar branches -- in every unrolled iteration; the fused CubeMLP forward spent
+// element carries the whole switch -- its activations, ~13 scalar branches -- in every unrolled iteration; the fused CubeMLP forward spent
 // ~200 cycles per element there (7.9 us of block 1's 50).  act_dispatch() branches ONCE around the loop: GELU (the model's activation) gets
 // its own straight-line copy, everything else the generic one.
 template <int ACT>

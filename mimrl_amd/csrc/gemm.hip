@@ -694,11 +694,24 @@ __device__ __forceinline__ void fast_body(const GemmDesc& d, int ksplit, int kt_
       return;
     }
   }
+  if constexpr (GEN) {
+    // constant tile indices, not an unrolled loop: four inlined GEN epilogues sit at the size limit of `#pragma unroll` (three more cases in
+    // the activation switch were enough to cross it), and a loop left rolled indexes acc[i][j] at run time: all accumulators in scratch
+    static_assert(TM <= 2 && TN <= 2, "the epilogue calls below cover 2 x 2 tiles per wave");
+    auto tile = [&](auto I, auto J) __attribute__((always_inline)) {
+      constexpr int i = decltype(I)::value, j = decltype(J)::value;
+      if constexpr (i < TM && j < TN)
+        epilogue<true>(d, d.atomic || ksplit > 1, bz, oc, bn_pre[j], acc[i][j], m0 + wm * 32 * TM + i * 32, n0 + wn * 32 * TN + j * 32 + (lane & 31), lane);
+    };
+    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
+    tile(I0{}, I0{}); tile(I0{}, I1{}); tile(I1{}, I0{}); tile(I1{}, I1{});
+  } else {
 #pragma unroll
-  for (int i = 0; i < TM; ++i)
+    for (int i = 0; i < TM; ++i)
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
-      epilogue<GEN>(d, d.atomic || ksplit > 1, bz, oc, bn_pre[j], acc[i][j], m0 + wm * 32 * TM + i * 32, n0 + wn * 32 * TN + j * 32 + (lane & 31), lane);
+      for (int j = 0; j < TN; ++j)
+        epilogue<false>(d, d.atomic || ksplit > 1, bz, oc, bn_pre[j], acc[i][j], m0 + wm * 32 * TM + i * 32, n0 + wn * 32 * TN + j * 32 + (lane & 31), lane);
+  }
 }
 
 template <int TM, int TN, bool AKC, bool BKC, bool GEN>
@@ -972,6 +985,7 @@ int gemm(hipStream_t s, const GemmDesc& d, bool bf16) {
   static const int dbg_skip = dbg_env("MIMRL_DBG_SKIP_WGRAD") ? atoi(dbg_env("MIMRL_DBG_SKIP_WGRAD")) : 0;   // timing experiments only
   if (dbg_skip && d.atomic && (dbg_skip == 1 || (dbg_skip == 2 && d.batch > 1 && d.sc_b == 0))) return MIMRL_OK;
   if (!d.A || !d.B || !d.C) return set_error(MIMRL_ERR_ARG, "gemm: null operand");
+  if (d.act < ACT_NONE || d.act > ACT_HARDTANH) return set_error(MIMRL_ERR_ARG, "gemm: activation %d outside [0, %d]", d.act, (int)ACT_HARDTANH);
   if ((d.A2 != nullptr) != (d.B2 != nullptr)) return set_error(MIMRL_ERR_ARG, "gemm: second product needs both operands");
   if (d.a_gap_rows && (d.a_gap_at % 4 != 0 || d.a_gap_rows % 4 != 0 || d.A2))
     return set_error(MIMRL_ERR_ARG, "gemm: the A-row gap must be a multiple of 4 rows (single product only)");

@@ -17,6 +17,9 @@ int validate_cfg(const mimrl_cfg& c) {
   if (c.d_common != 128)
     return set_error(MIMRL_ERR_ARG, "d_common must be 128 (the reference hard-codes embed_dim=128, Model.py:285; got %d)",
                      c.d_common);
+  if (c.activation < MIMRL_ACT_NONE || c.activation > MIMRL_ACT_HARDTANH)
+    return set_error(MIMRL_ERR_ARG, "activation %d outside [MIMRL_ACT_NONE = %d, MIMRL_ACT_HARDTANH = %d]", c.activation, MIMRL_ACT_NONE,
+                     MIMRL_ACT_HARDTANH);
   if (c.seq_len < 1 || c.seq_len > c.time_len) return set_error(MIMRL_ERR_ARG, "need 1 <= seq_len <= time_len");
   if (c.n_blocks < 1 || c.n_blocks > MIMRL_MAX_BLOCKS) return set_error(MIMRL_ERR_ARG, "1..%d CubeMLP blocks", MIMRL_MAX_BLOCKS);
   if (c.critic_type != MIMRL_CRITIC_SEPARATE && c.critic_type != MIMRL_CRITIC_CONCAT)
