@@ -349,6 +349,18 @@ int mimrl_op_class_loss(void* stream, int kind, const float* logits, const float
  * beside a running step does not occupy the whole chip); 0 = the library's choice.  Same bytes for every max_workgroups. */
 int mimrl_op_gather_rows(void* stream, int n_arrays, const void* const* src, void* const* dst, const int64_t* row_bytes, int64_t src_rows,
                          const int32_t* idx, int rows, int max_workgroups);
+/* Batch upload of a PACKED dataset (the frames of all samples back to back, no padding) for up to four arrays in ONE launch: row r of dst[a]
+ * is frames[a] frames of frame_bytes[a] bytes; its first min(length[a][i], frames[a]) frames come from src[a] at frame start[a][i], where
+ * i = idx[r], and the rest of the row is zero.  start[a] / length[a] are DEVICE arrays of src_rows entries, or both NULL: array a is dense
+ * and row i (frames[a] * frame_bytes[a] bytes) is copied whole, as mimrl_op_gather_rows does (src_frames[a] is not read then).  src, dst,
+ * frame_bytes, frames, start, length and src_frames are HOST arrays of n_arrays (1..4) entries, idx [rows] is DEVICE memory; frame_bytes[a]
+ * is a positive multiple of 4, frames[a] >= 1, the base addresses are 4-byte aligned (16 or 8 bytes per lane where frame length and both
+ * addresses allow it).  A sample that cannot be honoured -- i outside [0, src_rows), or in any packed array start < 0, length < 0 or
+ * start + length > src_frames[a] -- is never used as an address (start and length are read only after the range check on i): destination
+ * row r is filled with NaN in every array, the other rows are unaffected.  max_workgroups as for mimrl_op_gather_rows. */
+int mimrl_op_gather_packed(void* stream, int n_arrays, const void* const* src, void* const* dst, const int64_t* frame_bytes,
+                           const int32_t* frames, const int64_t* const* start, const int32_t* const* length, const int64_t* src_frames,
+                           int64_t src_rows, const int32_t* idx, int rows, int max_workgroups);
 /* fused ReLU-MLP stack (critic towers VMI.py:13-22, CMI classifier Model.py:47-72), bf16 MFMA, fp32 in/out.
  * W[l] is [dims[l+1], dims[l]] row-major, group g at + g*pstride (same for b[l], db[l]); activations are
  * [nb, brows, width].  forward: act[l] (l < nl-1) = post-ReLU outputs, out = linear top layer.

@@ -35,6 +35,7 @@ _EXTRA_FLAGS = [
     ("host_anchors", _FLAG, None),                      # draw kNN anchors with numpy's global RNG exactly like Model.py:81
     ("host_data", _FLAG, None),                         # keep the dataset in (pinned) host memory; default: resident in HBM when it fits
     ("shuffle", _FLAG, None),                           # a fresh permutation of the training set every pass (the reference's shuffle=True)
+    ("data_file", _STR, ""),                            # train on this packed dataset file (.npz; README "Datasets") instead of synthetic data
     ("synthetic_n", _INT, 1284),                        # --dataset synthetic: number of training samples (MOSI-sized)
     ("d_t", _INT, 768), ("d_a", _INT, 74), ("d_v", _INT, 35),
 ]

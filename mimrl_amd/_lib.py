@@ -116,6 +116,8 @@ def load() -> C.CDLL:
     lib.mimrl_op_class_loss.argtypes = [_FP, C.c_int, _FP, _FP, _FP, _FP, C.c_int, C.c_int]
     lib.mimrl_op_gather_rows.argtypes = [_FP, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int64, _FP,
                                          C.c_int, C.c_int]
+    lib.mimrl_op_gather_packed.argtypes = [_FP, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int64, _FP, C.c_int, C.c_int]
     lib.mimrl_main_late_offset.argtypes = [_FP]
     lib.mimrl_main_late_offset.restype = C.c_int64
     lib.mimrl_op_gemm16.argtypes = [_FP, _FP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), _FP, _FP, C.c_int,
@@ -189,6 +191,7 @@ EXPORTS = [
     "mimrl_probe_cube", "mimrl_probe_mi", "mimrl_probe_cmi", "mimrl_probe_knn", "mimrl_probe_encoders", "mimrl_set_kernel_stamps", "mimrl_comm_unique_id", "mimrl_set_comm", "mimrl_main_late_offset", "mimrl_set_comm_critic_bf16",
     "mimrl_stage1_pipe_prime", "mimrl_stage1_pipe", "mimrl_set_task_loss", "mimrl_op_task_loss", "mimrl_set_class_loss", "mimrl_op_class_loss",
     "mimrl_op_mi_infonce_rows", "mimrl_op_lstm_forward", "mimrl_op_lstm_backward", "mimrl_op_recur_btv", "mimrl_op_gather_rows",
+    "mimrl_op_gather_packed",
     "mimrl_op_adam_ex", "mimrl_op_frag_images",
 ]
 

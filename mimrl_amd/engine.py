@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import Buffers, MimrlError, check
-from .data import Rows
+from .data import Packed, Rows
 
 
 # the task losses that are means of per-row terms (exact under data parallelism with equal shards); the rest couple the batch
@@ -172,26 +172,49 @@ class HipEngine:
 
     def _put_rows(self, dsts, srcs, stream):
         """Enqueue, on ``stream`` (the CURRENT torch stream of the caller), the copy of a batch with ``data.Rows`` in it into the input set
-        ``dsts``.  Four Rows over device-resident bases sharing one ``idx``: ONE mimrl_op_gather_rows straight into the set, no temporary.
-        Four Rows over host bases: gathered on the host into the engine's pinned staging tensors (allocated once; reused only after the
-        upload that last read them), then the usual host-to-device copies.  Anything else (a mix of Rows and tensors, different index
-        tensors): the Rows are materialized and copied like tensors."""
+        ``dsts``.  Four Rows over device-resident bases sharing one ``idx``: ONE mimrl_op_gather_rows straight into the set, no temporary;
+        with ``data.Packed`` among them (a packed dataset: ragged samples, padded here) ONE mimrl_op_gather_packed, the dense labels riding
+        along.  Four Rows over host bases: gathered (Packed: padded) on the host into the engine's pinned staging tensors (allocated once;
+        reused only after the upload that last read them), then the usual host-to-device copies.  Anything else (a mix of Rows and
+        tensors, different index tensors): the Rows are materialized and copied like tensors."""
         B = dsts[3].shape[0]
         rows = all(isinstance(s, Rows) for s in srcs)
         if rows:
             idx = srcs[0].idx
             rows = all(s.idx is idx for s in srcs) and idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous()
+        packed = rows and any(isinstance(s, Packed) for s in srcs)
         if rows:
             if len(idx) != B:
                 raise MimrlError(f"a batch of {len(idx)} rows for an engine of batch size {B}")
+            samples = lambda s: s.start.shape[0] if isinstance(s, Packed) else s.base.shape[0]
             for d, s in zip(dsts, srcs):
                 b = s.base
-                if b.dtype != torch.float32 or not b.is_contiguous() or b.dim() < 1 or b.shape[0] < 1 or b.numel() // b.shape[0] != d.numel() // B:
+                if isinstance(s, Packed):
+                    if b.dtype != torch.float32 or not b.is_contiguous() or b.dim() != 2 or tuple(d.shape[1:]) != (s.T, b.shape[1]):
+                        raise MimrlError(f"Packed frames {tuple(b.shape)} {b.dtype} padded to {s.T} do not fit an input of shape {tuple(d.shape)}: "
+                                         f"contiguous float32 frames of the input's width and its sequence length are needed")
+                    if (s.start.dtype != torch.int64 or s.length.dtype != torch.int32 or s.start.dim() != 1 or s.start.shape != s.length.shape
+                            or not s.start.is_contiguous() or not s.length.is_contiguous() or s.start.device != idx.device or s.length.device != idx.device):
+                        raise MimrlError("Packed needs contiguous int64 starts and int32 lengths, one per sample, on the device of its sample numbers")
+                elif b.dtype != torch.float32 or not b.is_contiguous() or b.dim() < 1 or b.shape[0] < 1 or b.numel() // b.shape[0] != d.numel() // B:
                     raise MimrlError(f"Rows over a {tuple(b.shape)} {b.dtype} tensor do not fit an input of shape {tuple(d.shape)}: contiguous "
                                      f"float32 rows of the same length are needed")
-                if b.device != idx.device or b.shape[0] != srcs[0].base.shape[0]:
+                if b.device != idx.device or samples(s) != samples(srcs[0]):
                     raise MimrlError("the Rows of a batch must index datasets of one length on the device of their row numbers")
-        if rows and self.GATHER_ROWS and idx.is_cuda and self.device.index in (None, idx.device.index):
+        on_device = rows and self.GATHER_ROWS and idx.is_cuda and self.device.index in (None, idx.device.index)
+        if on_device and packed and all(s.base.shape[0] > 0 for s in srcs):
+            meta = tuple((s.start.data_ptr(), s.length.data_ptr(), s.T, s.base.shape[0]) if isinstance(s, Packed) else (None, None, 1, 0) for s in srcs)
+            key = tuple(s.base.data_ptr() for s in srcs) + tuple(d.data_ptr() for d in dsts) + meta
+            cache = self.__dict__.setdefault("_gather_args", {})
+            if key not in cache:
+                cache[key] = ((C.c_void_p * 4)(*key[:4]), (C.c_void_p * 4)(*key[4:8]),
+                              (C.c_int64 * 4)(*(4 * (d.numel() // B) // m[2] for d, m in zip(dsts, meta))), (C.c_int32 * 4)(*(m[2] for m in meta)),
+                              (C.c_void_p * 4)(*(m[0] for m in meta)), (C.c_void_p * 4)(*(m[1] for m in meta)), (C.c_int64 * 4)(*(m[3] for m in meta)))
+            check(self.lib.mimrl_op_gather_packed(C.c_void_p(stream.cuda_stream), 4, *cache[key], int(samples(srcs[0])),
+                                                  _ptr(idx), B, int(self.GATHER_MAX_WORKGROUPS)))
+            self._gather_keep = (idx, srcs)             # alive until the next gather: the launch above reads them asynchronously
+            return
+        if on_device and not packed:
             key = tuple(s.base.data_ptr() for s in srcs) + tuple(d.data_ptr() for d in dsts)
             cache = self.__dict__.setdefault("_gather_args", {})
             if key not in cache:
@@ -209,7 +232,10 @@ class HipEngine:
                 self._host_stage_ev.record(stream)
             self._host_stage_ev.synchronize()           # the upload that last read the staging tensors is over
             for st, s, d in zip(self._host_stage, srcs, dsts):
-                torch.index_select(s.base.reshape(s.base.shape[0], -1), 0, idx, out=st.view(B, -1))
+                if isinstance(s, Packed):
+                    s.materialize(out=st)
+                else:
+                    torch.index_select(s.base.reshape(s.base.shape[0], -1), 0, idx, out=st.view(B, -1))
                 d.copy_(st, non_blocking=True)
             self._host_stage_ev.record(stream)
             return
