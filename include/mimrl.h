@@ -361,6 +361,29 @@ int mimrl_op_gather_rows(void* stream, int n_arrays, const void* const* src, voi
 int mimrl_op_gather_packed(void* stream, int n_arrays, const void* const* src, void* const* dst, const int64_t* frame_bytes,
                            const int32_t* frames, const int64_t* const* start, const int32_t* const* length, const int64_t* src_frames,
                            int64_t src_rows, const int32_t* idx, int rows, int max_workgroups);
+/* Running scores (Utils.py:118-175 calc_metrics; Solver.py:345-356 for classification): fold n rows into the sufficient statistics in acc,
+ * a caller-owned DEVICE block of MIMRL_SCORE_SLOTS 8-byte slots (8-byte aligned) that the caller zeroes to reset.  Slots below
+ * MIMRL_SC_N are doubles, the rest int64.
+ * num_class = 0, the regression table of pred[n] against y[n]: Chan / Welford running moments of the float64 images of the fp32 values
+ * (means, centred sums of squares M2, centred cross sum C, and the sum of |p - y|), the row count, the Acc-7 / Acc-5 hits
+ * (rint(clip(p, +-3)) == rint(clip(y, +-3)), and +-2; half to even), the pos/neg confusion over the rows with y != 0 (truth y > 0,
+ * prediction p > 0) and the nneg/neg confusion over all rows (y >= 0, p >= 0), both indexed 2 * truth + prediction.  A NaN prediction
+ * misses every accuracy (it is counted as the class the truth is not) and makes the moments NaN.
+ * num_class = 1 .. MIMRL_MAX_CLASSES, classification with pred as [n, num_class] logits: truth rint(y), prediction logit > 0 (one class) or
+ * the FIRST maximal logit; Ceff = max(num_class, 2); confusion cell truth * Ceff + prediction at MIMRL_SC_CONF.  A row whose label is not in
+ * [0, Ceff) counts in MIMRL_SC_IGNORED and in nothing else.  The double slots are not touched.
+ * One workgroup, no atomics, a fixed reduction order: the same calls give the same bits.  1 <= n <= 2^20. */
+enum {
+  MIMRL_SC_MEAN_P = 0, MIMRL_SC_MEAN_Y = 1, MIMRL_SC_M2_P = 2, MIMRL_SC_M2_Y = 3, MIMRL_SC_C_PY = 4, MIMRL_SC_SUM_ABS = 5,
+  MIMRL_SC_N = 6,          /* rows counted (classification: without the ignored ones) */
+  MIMRL_SC_ACC7 = 7, MIMRL_SC_ACC5 = 8,
+  MIMRL_SC_PN = 9,         /* 4 cells */
+  MIMRL_SC_NN = 13,        /* 4 cells */
+  MIMRL_SC_IGNORED = 17,
+  MIMRL_SC_CONF = 18,      /* MIMRL_MAX_CLASSES x MIMRL_MAX_CLASSES cells at most */
+  MIMRL_SCORE_SLOTS = 82
+};
+int mimrl_op_score_accum(void* stream, int num_class, const float* pred, const float* y, int n, void* acc);
 /* fused ReLU-MLP stack (critic towers VMI.py:13-22, CMI classifier Model.py:47-72), bf16 MFMA, fp32 in/out.
  * W[l] is [dims[l+1], dims[l]] row-major, group g at + g*pstride (same for b[l], db[l]); activations are
  * [nb, brows, width].  forward: act[l] (l < nl-1) = post-ReLU outputs, out = linear top layer.

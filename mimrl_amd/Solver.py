@@ -22,7 +22,7 @@ from .data import Rows, plain
 from .Customization import compute_custumized_loss, compute_outputs_from_model, other_model_operations
 from .engine import HipEngine
 from .Model import Model
-from .Utils import TASK_LOSS_FUNCTIONS, log_message, set_logger, weighted_f1
+from .Utils import TASK_LOSS_FUNCTIONS, log_message, regression_scores, score_from_block, set_logger, weighted_f1
 
 
 class _Plateau:
@@ -84,6 +84,8 @@ class Solver:
         self._tails = {}                 # batch size -> engine sharing self.engine's buckets (partial last batch)
         self._active = self.engine
         self._want_prefetch = False
+        self.track_score = False         # step(): fold every batch's predictions into a score block (read_score); off = no extra launch
+        self._step_score = None
         if self.world > 1:      # identical replicas: rank 0's initial parameters everywhere
             mdist.broadcast_(self.engine.main["p"])
             mdist.broadcast_(self.engine.crit["p"])
@@ -270,11 +272,33 @@ class Solver:
             mdist.ddp_two_stage_step(e, self.world)
         else:
             e.step()              # mimrl_two_stage_step: both stages as one captured graph
+        if self.track_score:
+            if self._step_score is None:
+                self._step_score = self.engine.new_score_block()
+            e.score_accum(self._step_score)
         sc = e.scalars
         return sc[_lib.S1_LOSS], sc[_lib.S2_LOSS], sc[_lib.S2_MIS:_lib.S2_MIS + 8], e.pred.reshape(e.pred.shape[0], -1)
 
+    def read_score(self, reset=True):
+        """The score dict (``get_score_from_result``'s keys) of the predictions of every ``step()`` since ``track_score`` was set, or since
+        the last ``read_score(reset=True)``: each step folded its batch into a block on the device (HipEngine.score_accum); this is the one
+        point that copies it to the host, and so the only sync.  Rank-local under data parallelism."""
+        if self._step_score is None:
+            raise _lib.MimrlError("read_score: no score was tracked -- set Solver.track_score = True before the step() calls to be scored")
+        block = self._step_score.cpu().numpy()
+        if reset:
+            self._step_score.zero_()
+        return self._score_from_block(block)
+
+    def _score_from_block(self, block):
+        task = getattr(self.opt, "task", "regression")
+        return score_from_block(block, int(getattr(self.opt, "num_class", 1)), task)
+
     # ------------------------------------------------------------------ Solver.train (Solver.py:194-248)
     def train(self, epoch, train_loader, C_F_all, F_F_all, T_F_all, A_F_all, V_F_all):
+        """-> (stage-2 loss, stage-1 loss, MI means, train score, the five banks of this pass).  The train score is accumulated on the
+        device, batch by batch of the model pass (HipEngine.score_accum), and is rank-local under data parallelism: every rank scores
+        the predictions of its own shard; nothing reduces the block across ranks."""
         self.model.train()
         self._prefetch(False)                                                  # epoch-ordered passes: stages see different batches
         self._apply_lr(epoch)
@@ -291,22 +315,20 @@ class Solver:
                     self._stage(e, 1)
                     acc[_lib.S1_LOSS] += e.scalars[_lib.S1_LOSS]
         new = {k: [] for k in "CFTAV"}
-        preds, targs = [], []
+        score = self.engine.new_score_block()
         for e, datas in self._iter_loaded(train_loader):
             self._anchors(e, 2)
             self._stage(e, 2)
             new["C"].append(e.labels.reshape(-1, 1).clone())                   # Solver.py:223-227 (features of THIS pass)
             for i, k in enumerate("FTAV"):
                 new[k].append(e.feats[i].clone())
-            preds.append(e.pred.clone())
-            targs.append(e.labels.clone())
+            e.score_accum(score)           # (here: the read of e.labels stays ahead of the upload that recycles the idle input set)
             acc[32:] += e.scalars[32:]
         banks = [torch.cat(new[k], 0) for k in "CFTAV"]
         if self.world > 1:                                                    # banks are replicated
             banks = [mdist.allgather_rows(x, self.world) for x in banks]
-        a = acc.cpu().numpy()                                                 # the ONE read-back of the epoch
-        predictions, targets = torch.cat(preds).cpu().numpy().reshape(-1, self.engine.num_class), torch.cat(targs).cpu().numpy().reshape(-1, 1)
-        train_score = self.get_score_from_result(predictions, targets)
+        a = acc.cpu().numpy()                                                 # the ONE read-back of the epoch: the sums and the score block
+        train_score = self._score_from_block(score.cpu().numpy())
         mis = [float(x) / nb for x in a[_lib.S2_MIS:_lib.S2_MIS + 8]]
         return (float(a[_lib.S2_LOSS]) / nb, float(a[_lib.S1_LOSS]) / nb, mis, train_score, *banks)
 
@@ -316,11 +338,13 @@ class Solver:
         self._prefetch(False)
         self._set_banks(C_F_all, F_F_all, T_F_all, A_F_all, V_F_all)
         acc = torch.zeros(_lib.NSCALARS, device=self.engine.device)
+        score_blk = self.engine.new_score_block()
         preds, targs, feats = [], [], []
         for e, datas in self._iter_loaded(valid_loader, training=False):
             self._anchors(e, 2)
             e.forward(train=False, with_losses=True)
             acc += e.scalars
+            e.score_accum(score_blk)
             preds.append(e.pred.clone())
             targs.append(e.labels.clone())
             if self.opt.save_best_features:
@@ -329,7 +353,7 @@ class Solver:
         nb = len(valid_loader)
         predictions = torch.cat(preds).cpu().numpy().reshape(-1, self.engine.num_class)
         targets = torch.cat(targs).cpu().numpy().reshape(-1, 1)
-        score = self.get_score_from_result(predictions, targets)
+        score = self._score_from_block(score_blk.cpu().numpy())                # (one code path for every score: the block, not the arrays)
         mis = [float(x) / nb for x in a[_lib.S2_MIS:_lib.S2_MIS + 8]]
         return float(a[_lib.S2_LOSS]) / nb, mis, score, predictions, targets, feats
 
@@ -352,17 +376,16 @@ class Solver:
 
     # ------------------------------------------------------------------ cold path
     def get_score_from_result(self, predictions, targets):
-        """Regression: mae / corr of Utils.calc_metrics (Utils.py:135-136).  Classification (Solver.py:345-356): accuracy and the weighted
-        F1 of the argmax (one class: logit > 0) against the class indices."""
+        """Regression: the table of Utils.calc_metrics (Utils.py:118-175; ``Utils.regression_scores``): mae, corr, 7-class_acc, 5-class_acc and
+        accuracy / weighted F1 of the pos/neg and nneg/neg splits, in that order.  Classification (Solver.py:345-356): accuracy and the
+        weighted F1 of the argmax (one class: logit > 0) against the class indices.  The host formula; train / evaluate / step get the same
+        numbers from a score block accumulated on the device (``Utils.score_from_block``)."""
         if getattr(self.opt, "task", "regression") == "classification":
             C = int(self.opt.num_class)
             pred = (predictions.reshape(-1) > 0).astype(np.int64) if C == 1 else predictions.reshape(-1, C).argmax(1)
             t = np.rint(targets.reshape(-1)).astype(np.int64)
             return {f"{C}-class_acc": float((pred == t).mean()), f"{C}-f1": weighted_f1(t, pred)}
-        p, t = predictions.reshape(-1).astype(np.float64), targets.reshape(-1).astype(np.float64)
-        mae = float(np.abs(p - t).mean())
-        corr = float(np.corrcoef(p, t)[0, 1]) if p.std() > 0 and t.std() > 0 else 0.0
-        return {"mae": mae, "corr": corr}
+        return regression_scores(predictions, targets)
 
     def current_result_better(self, best, current):
         if getattr(self.opt, "task", "regression") == "classification":                          # Solver.py:428-429: accuracy, upwards
@@ -452,7 +475,8 @@ class Solver:
 
     def solve(self):
         """Solver.py:38-105: epoch loop, best-valid / best-test tracking, checkpoints and prediction files (rank 0).
-        TensorBoard and the class-accuracy metric tables are outside the hot path."""
+        The scores of every split are the reference's metric table (``get_score_from_result``); the log shows the training mae and every
+        validation / test item.  TensorBoard is outside the hot path."""
         if self.rank == 0:
             os.makedirs(self.task_path, exist_ok=True)
             set_logger(os.path.join(self.task_path, "Running.log"))

@@ -21,6 +21,11 @@ NSCALARS = 64
 MAX_CLASSES = 8             # MIMRL_MAX_CLASSES: outputs of the classification head
 PHASES = ["gemm_misc", "gru_fwd", "gru_bwd", "cube_fwd", "cube_bwd", "est_fwd", "est_bwd", "opt", "model_misc"]
 S1_LOSS, S1_MIS, S1_LOSSES, S2_LOSS, S2_TASK, S2_MIS, S2_LOSSES = 0, 1, 12, 32, 33, 34, 42
+# MIMRL_SC_*: the 8-byte slots of a score block (mimrl_op_score_accum); doubles below SC_N, int64 from there on
+SC_MEAN_P, SC_MEAN_Y, SC_M2_P, SC_M2_Y, SC_C_PY, SC_SUM_ABS = 0, 1, 2, 3, 4, 5
+SC_N, SC_ACC7, SC_ACC5, SC_PN, SC_NN, SC_IGNORED, SC_CONF = 6, 7, 8, 9, 13, 17, 18
+SCORE_SLOTS = 82            # MIMRL_SCORE_SLOTS
+SCORE_MAX_ROWS = 1 << 20    # rows of one mimrl_op_score_accum call
 
 BOUNDS = {"infonce": 0, "nwj": 1, "tuba": 2, "dv": 3, "js_fgan": 4, "js": 5, "smile": 6, "mine": 7, "interpolate": 8}
 ACTS = {"none": 0, "relu": 1, "gelu": 2, "tanh": 3, "elu": 4, "leakyrelu": 5, "hardtanh": 6}      # MIMRL_ACT_*
@@ -118,6 +123,7 @@ def load() -> C.CDLL:
                                          C.c_int, C.c_int]
     lib.mimrl_op_gather_packed.argtypes = [_FP, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                            C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int64, _FP, C.c_int, C.c_int]
+    lib.mimrl_op_score_accum.argtypes = [_FP, C.c_int, _FP, _FP, C.c_int, _FP]
     lib.mimrl_main_late_offset.argtypes = [_FP]
     lib.mimrl_main_late_offset.restype = C.c_int64
     lib.mimrl_op_gemm16.argtypes = [_FP, _FP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), _FP, _FP, C.c_int,
@@ -191,7 +197,7 @@ EXPORTS = [
     "mimrl_probe_cube", "mimrl_probe_mi", "mimrl_probe_cmi", "mimrl_probe_knn", "mimrl_probe_encoders", "mimrl_set_kernel_stamps", "mimrl_comm_unique_id", "mimrl_set_comm", "mimrl_main_late_offset", "mimrl_set_comm_critic_bf16",
     "mimrl_stage1_pipe_prime", "mimrl_stage1_pipe", "mimrl_set_task_loss", "mimrl_op_task_loss", "mimrl_set_class_loss", "mimrl_op_class_loss",
     "mimrl_op_mi_infonce_rows", "mimrl_op_lstm_forward", "mimrl_op_lstm_backward", "mimrl_op_recur_btv", "mimrl_op_gather_rows",
-    "mimrl_op_gather_packed",
+    "mimrl_op_gather_packed", "mimrl_op_score_accum",
     "mimrl_op_adam_ex", "mimrl_op_frag_images",
 ]
 

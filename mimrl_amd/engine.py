@@ -434,6 +434,20 @@ class HipEngine:
         self._coherent()
         check(self.lib.mimrl_forward(self.handle, int(train), int(with_losses)))
 
+    def new_score_block(self) -> torch.Tensor:
+        """A zeroed score block (``_lib.SCORE_SLOTS`` 8-byte slots, ``_lib.SC_*``) on this engine's device; ``zero_()`` resets it."""
+        return torch.zeros(_lib.SCORE_SLOTS, dtype=torch.float64, device=self.device)
+
+    def score_accum(self, acc: torch.Tensor):
+        """Fold the current ``pred`` against the current ``labels`` into the score block ``acc`` (include/mimrl.h: mimrl_op_score_accum)
+        on the engine's stream, behind whatever wrote them: the regression table, or under a classification loss the confusion matrix of
+        ``cfg.num_class`` classes.  No sync; ``Utils.score_from_block`` turns the block, read back, into the score dict."""
+        if acc.dtype != torch.float64 or acc.numel() != _lib.SCORE_SLOTS or not acc.is_contiguous() or acc.device != self.pred.device:
+            raise MimrlError(f"score_accum: the block must be {_lib.SCORE_SLOTS} contiguous float64 slots on {self.pred.device}")
+        ncls = int(self.cfg.num_class) if self.task_loss in _lib.CLASS_LOSSES.values() else 0
+        check(self.lib.mimrl_op_score_accum(C.c_void_p(self.stream.cuda_stream), ncls, _ptr(self.pred), _ptr(self.labels),
+                                            int(self.cfg.batch), _ptr(acc)))
+
     def estimate(self, stage: int):
         """Estimators only, on the features left by the last forward (Model.compute_vmi_loss_stage1/2)."""
         self._coherent()
