@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <vector>
 #include <dlfcn.h>
@@ -99,6 +100,15 @@ struct Lin { long w = -1, b = -1; int out = 0, in = 0; };
 struct GruDirW { long w_ih = 0, w_hh = 0, b_ih = 0, b_hh = 0; int din = 0; };
 struct AxisW { Lin fc1, fc2; long res = -1, ln_g = -1, ln_b = -1; int in = 0, hid = 0, out = 0; };
 struct BlockW { AxisW ax[3]; };
+// sizes of one CubeMLP block: input / hidden / output length of the L, K and D axis (mimrl_handle::shape(i) reads them from blk[i].ax[])
+struct BlockShape {
+  int il, hl, ol, ik, hk, ok, id, hd, od;
+  long C() const { return (long)ik * id; }                           // columns of a sample's L-axis tile [., C]
+  long rows_d(long B) const { return B * ol * ok; }                  // rows of the D-axis products
+  int hl_pad4() const { return (hl + 3) & ~3; }                      // row pitch of the padded L-axis fc2 copy (w2p)
+  size_t in_count(size_t B) const { return B * il * ik * id; }       // elements of the block's input ...
+  size_t out_count(size_t B) const { return B * ol * ok * od; }      // ... and of its output
+};
 struct MixBuf { float *xn = nullptr, *xn_mean = nullptr, *xn_rstd = nullptr, *u = nullptr, *h = nullptr, *y = nullptr,
                       *z = nullptr, *mean = nullptr, *rstd = nullptr; };
 struct BlockBuf { MixBuf l, k, d; };
@@ -188,6 +198,10 @@ struct mimrl_handle {
   GruDirW gru[2][2][2];          // [mod a=0,v=1][layer][dir]
   long ln_g[2], ln_b[2], w_t;
   BlockW blk[MIMRL_MAX_BLOCKS];
+  BlockShape shape(int i) const {      // (valid once resolve() has run, i.e. before the workspace is carved)
+    const AxisW* a = blk[i].ax;
+    return BlockShape{a[0].in, a[0].hid, a[0].out, a[1].in, a[1].hid, a[1].out, a[2].in, a[2].hid, a[2].out};
+  }
   long cls_w, cls_b;
   // bf16 images of the critic bucket for the fused estimator stacks: straight (kept fresh by the critic Adam launch, rebuilt
   // after mimrl_bind / mimrl_params_changed) and per-matrix transposed (rebuilt beside every estimator forward pass)
@@ -519,16 +533,32 @@ struct mimrl_handle {
   int G_(const GemmDesc& d) { return G_on(stream, d); }
   // weight-gradient work parked by cube_backward and issued on the side streams once the data-gradient chain is through
   // (it then overlaps the latency-bound GRU BPTT instead of competing with the chain for CUs and L2)
-  struct Deferred { int kind; int side; GemmDesc g; const float* src; long n0, n1, n2, n3; float* dst;
-                    const float *p1 = nullptr, *p2 = nullptr, *p3 = nullptr; float* dst2 = nullptr; KMixW kw = KMixW();
-                    const float *p4 = nullptr, *p5 = nullptr; float *dst3 = nullptr, *dst4 = nullptr; };
-  std::vector<Deferred> deferred;
+  // (the values are the bit positions of MIMRL_DBG_SKIP_DEFERRED)
+  enum ParkedKind { PARK_GEMM = 0, PARK_COLSUM = 1, PARK_ROWSUM = 2, PARK_LN_PARAMS = 3, PARK_KMIX_PARAMS = 5, PARK_DAXIS_PARAMS = 6 };
+  struct Parked {
+    ParkedKind kind; int side;
+    GemmDesc g;                                  // PARK_GEMM only: what the grouped split-K launch of flush_deferred reads
+    std::function<int(hipStream_t)> launch;      // the launch itself, its arguments captured by value
+  };
+  std::vector<Parked> deferred;
   int flush_deferred(int only_side = 0);
   int wg_helper = -1;                  // side stream for weight-gradient GEMMs of an MLP stack beside the data-gradient chain / the grouped launch (-1: none)
   int dbg_delay(hipStream_t st, int tag);   // critical-path probe (sw.dbg_delay_tag / _us): a spin kernel behind one phase
   int model_forward(bool train, bool save, int knn_stage = 0, int part = 0);   // part: 0 all, 1 prefix, 2 tail
   int cube_forward(bool train, bool save, const CubePre* pre = nullptr, const CubeHead* head = nullptr);   // pre / head: fold the tail's bookends into block 0 / the last block
   bool cube_block_fused(int i, bool train) const;   // block i of cube_forward takes the one-kernel path (cube_fused.hip)
+  // K-axis weights of block i as kmix_fwd / kmix_bwd take them (a kernel argument: zero-filled first, dbg included); the gradient slots are the caller's
+  KMixW kmix_w(int i, float drop_p) const {
+    const AxisW& a = blk[i].ax[1];
+    KMixW kw;
+    std::memset(&kw, 0, sizeof kw);
+    kw.w1 = P(a.fc1.w); kw.b1 = a.fc1.b >= 0 ? P(a.fc1.b) : nullptr;
+    kw.w2 = P(a.fc2.w); kw.b2 = a.fc2.b >= 0 ? P(a.fc2.b) : nullptr;
+    kw.wr = a.res >= 0 ? P(a.res) : nullptr; kw.g = P(a.ln_g); kw.be = P(a.ln_b);
+    kw.ik = a.in; kw.hk = a.hid; kw.ok = a.out; kw.act = cfg.activation; kw.ln_first = cfg.ln_first;
+    kw.drop_p = drop_p; kw.key = key(); kw.stream_id = 11 + 3 * i;
+    return kw;
+  }
   int cube_backward(int cur_in, int* cur_out);
   int wt_images(hipStream_t st, bool bwd_bf16, bool launch, bool* d_fused);
   int model_backward();

@@ -250,8 +250,7 @@ int mimrl_probe_cube(mimrl_handle* h, const float* x, float* out, const float* d
   if (dout && !dx) return set_error(MIMRL_ERR_ARG, "dout without dx");
   const mimrl_cfg& c = h->cfg;
   const int nb = c.n_blocks;
-  const size_t nin = (size_t)c.batch * c.time_len * 3 * c.d_common;
-  const size_t nout = (size_t)c.batch * c.d_outs[nb - 1][0] * c.d_outs[nb - 1][1] * c.d_outs[nb - 1][2];
+  const size_t nin = h->shape(0).in_count(c.batch), nout = h->shape(nb - 1).out_count(c.batch);
   h->ev_next = 0;
   HIPX(hipMemcpyAsync(h->cube0, x, sizeof(float) * nin, hipMemcpyDeviceToDevice, h->stream));
   h->bf16 = h->bf16_fwd();

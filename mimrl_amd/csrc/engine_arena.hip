@@ -160,28 +160,25 @@ int mimrl_handle::carve_fwd(size_t* gmax_out) {
   }
   MX(take(&cube0, B * L * 3 * D));
   size_t gmax = B * L * 3 * D;
-  int il = cfg.time_len, ik = 3, id = cfg.d_common;
   for (int i = 0; i < cfg.n_blocks; ++i) {
-    const int hl = cfg.d_hiddens[i][0], hk = cfg.d_hiddens[i][1], hd = cfg.d_hiddens[i][2];
-    const int ol = cfg.d_outs[i][0], ok = cfg.d_outs[i][1], od = cfg.d_outs[i][2];
-    (void)hk;
+    const BlockShape s = shape(i);
+    const size_t il = s.il, hl = s.hl, ol = s.ol, ok = s.ok, id = s.id, hd = s.hd, od = s.od;
     BlockBuf& b = bb[i];
-    const size_t C = (size_t)ik * id;
+    const size_t C = s.C();
     if (cfg.ln_first) { MX(take(&b.l.xn, B * il * C)); MX(take(&b.l.xn_mean, B * C)); MX(take(&b.l.xn_rstd, B * C)); }
     MX(take(&b.l.u, B * hl * C)); MX(take(&b.l.h, B * hl * C));
     MX(take(&b.l.y, B * ol * C));
     if (!cfg.ln_first) { MX(take(&b.l.z, B * ol * C)); MX(take(&b.l.mean, B * C)); MX(take(&b.l.rstd, B * C)); }
     else b.l.z = b.l.y;
     MX(take(&b.k.z, B * ol * ok * id));
-    const size_t R2 = B * ol * ok;
+    const size_t R2 = s.rows_d(B);
     if (cfg.ln_first) { MX(take(&b.d.xn, R2 * id)); MX(take(&b.d.xn_mean, R2)); MX(take(&b.d.xn_rstd, R2)); }
     MX(take(&b.d.u, R2 * hd)); MX(take(&b.d.h, R2 * hd));
     MX(take(&b.d.y, R2 * od));
     if (!cfg.ln_first) { MX(take(&b.d.z, R2 * od)); MX(take(&b.d.mean, R2)); MX(take(&b.d.rstd, R2)); }
     else b.d.z = b.d.y;
-    const size_t cand[] = {B * il * C, B * hl * C, B * ol * C, B * ol * ok * id, R2 * hd, R2 * od};
+    const size_t cand[] = {s.in_count(B), B * hl * C, B * ol * C, B * ol * ok * id, R2 * hd, s.out_count(B)};
     for (size_t c : cand) gmax = c > gmax ? c : gmax;
-    il = ol; ik = ok; id = od;
   }
   *gmax_out = gmax;
   return MIMRL_OK;
@@ -223,8 +220,8 @@ int mimrl_handle::carve() {
   }
   MX(take(&ff, B * D));
   for (int i = 0; i < cfg.n_blocks; ++i) {
-    const int hl = cfg.d_hiddens[i][0], ol = cfg.d_outs[i][0];
-    if (hl % 4 != 0) MX(take(&w2p[i], (size_t)ol * ((hl + 3) & ~3) + 64));
+    const BlockShape s = shape(i);
+    if (s.hl % 4 != 0) MX(take(&w2p[i], (size_t)s.ol * s.hl_pad4() + 64));
   }
   MX(take(&dpred, B * ncls()));
   if (cfg.encoder == MIMRL_ENCODER_GRU) {

@@ -3,10 +3,6 @@
 
 int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
   const int B = cfg.batch;
-  int dims[MIMRL_MAX_BLOCKS + 1][3];
-  dims[0][0] = cfg.time_len; dims[0][1] = 3; dims[0][2] = cfg.d_common;
-  for (int i = 0; i < cfg.n_blocks; ++i)
-    for (int ax = 0; ax < 3; ++ax) dims[i + 1][ax] = cfg.d_outs[i][ax];
   // deferred mode: every gradient buffer is used once (weight-gradient GEMMs read dY / dU after the chain has moved on)
   const int per_block = 7 + (cfg.dropout_mlp[0] > 0.f) + (cfg.dropout_mlp[2] > 0.f);   // buffers one block consumes
   const bool defer = multi_stream && !cfg.ln_first && per_block * cfg.n_blocks + 1 <= NGBUF;
@@ -16,37 +12,14 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
   int cur = cur_in;
   auto grab = [&]() { for (int q = 0; q < npool; ++q) if (!used[q]) { used[q] = 1; return q; } return -1; };
   auto release = [&](int q) { if (!defer) used[q] = 0; };
+  // parameter-gradient work: parked for flush_deferred, or -- not deferring -- launched on its side stream right here
+  auto park = [&](ParkedKind kind, int sd, std::function<int(hipStream_t)> launch, const GemmDesc& g = GemmDesc()) -> int {
+    if (!defer) return launch(S(sd));
+    deferred.push_back(Parked{kind, sd, g, std::move(launch)});
+    return MIMRL_OK;
+  };
   auto W_gemm = [&](int sd, const GemmDesc& g) -> int {
-    if (defer) { deferred.push_back(Deferred{0, sd, g, nullptr, 0, 0, 0, 0, nullptr}); return MIMRL_OK; }
-    return G_on(S(sd), g);
-  };
-  auto W_colsum = [&](int sd, const float* src, long rows, int cols, int ld, float* dst) -> int {
-    if (defer) { deferred.push_back(Deferred{1, sd, GemmDesc(), src, rows, cols, ld, 0, dst}); return MIMRL_OK; }
-    return colsum(S(sd), src, rows, cols, ld, dst);
-  };
-  auto W_rowsum = [&](int sd, const float* src, int nb, int rows, int cols, float* dst) -> int {
-    if (defer) { deferred.push_back(Deferred{2, sd, GemmDesc(), src, nb, rows, cols, 0, dst}); return MIMRL_OK; }
-    return rowsum_batched(S(sd), src, nb, rows, cols, dst);
-  };
-  auto W_lnpar = [&](int sd, const float* y, const float* mean, const float* rstd, const float* dz, float* dgam, float* dbet,
-                     int nb, int n, int cols) -> int {
-    if (defer) {
-      Deferred d{3, sd, GemmDesc(), y, nb, n, cols, 0, dgam};
-      d.p1 = mean; d.p2 = rstd; d.p3 = dz; d.dst2 = dbet;
-      deferred.push_back(d);
-      return MIMRL_OK;
-    }
-    return colln_param_grads(S(sd), y, mean, rstd, dz, dgam, dbet, nb, n, cols);
-  };
-  auto W_dpg = [&](int sd, const float* y, const float* mean, const float* rstd, const float* dz, const float* dy, const float* du,
-                   float* dgam, float* dbet, float* db2, float* db1, long rows) -> int {
-    if (defer) {
-      Deferred d{6, sd, GemmDesc(), y, rows, 0, 0, 0, dgam};
-      d.p1 = mean; d.p2 = rstd; d.p3 = dz; d.p4 = dy; d.p5 = du; d.dst2 = dbet; d.dst3 = db2; d.dst4 = db1;
-      deferred.push_back(d);
-      return MIMRL_OK;
-    }
-    return daxis_param_grads(S(sd), y, mean, rstd, dz, dy, du, dgam, dbet, db2, db1, rows);
+    return park(PARK_GEMM, sd, [this, g](hipStream_t st) { return G_on(st, g); }, g);
   };
   auto W_fork = [&](int lo, int hi) -> int { return defer ? MIMRL_OK : fork(lo, hi); };
   // transposed bf16 images of the D-axis weights for the fused data-gradient kernels (one small launch; in a combined step
@@ -61,15 +34,15 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
   for (int i = cfg.n_blocks - 1; i >= 0; --i) {
     const BlockW& w = blk[i];
     BlockBuf& b = bb[i];
-    const int il = dims[i][0], ik = dims[i][1], id = dims[i][2];
-    const int hl = w.ax[0].hid, ol = w.ax[0].out, hk = w.ax[1].hid, ok = w.ax[1].out, hd = w.ax[2].hid, od = w.ax[2].out;
+    const BlockShape s = shape(i);
+    const int il = s.il, hl = s.hl, ol = s.ol, id = s.id, hd = s.hd, od = s.od;
+    const long C = s.C(), R2 = s.rows_d(B);
     const float* xblk = i == 0 ? cube0 : bb[i - 1].d.z;
     const float pl = cfg.dropout_mlp[0], pk = cfg.dropout_mlp[1], pd = cfg.dropout_mlp[2];
     // ------------------------------------------------ D axis backward
     if (d_fused[i]) {
       // one launch: LayerNorm(D) backward -> dY -> dU -> dX (row tiles); weight / bias / LayerNorm gradients stay side work
       const AxisW& a = w.ax[2];
-      const long R2 = (long)B * ol * ok;
       GRAB(i_dy); GRAB(i_du); GRAB(i_dx);
       DAxisBwdArgs fa;
       fa.dz = gbuf[cur]; fa.y = b.d.y; fa.mean = b.d.mean; fa.rstd = b.d.rstd; fa.gamma = P(a.ln_g); fa.u = b.d.u;
@@ -81,8 +54,11 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
       fa.dgamma = fa.dbeta = fa.db2 = fa.db1 = nullptr;
       MX(daxis_bwd_fused(stream, fa));
       MX(W_fork(1, 3));
-      MX(W_dpg(2, b.d.y, b.d.mean, b.d.rstd, gbuf[cur], gbuf[i_dy], gbuf[i_du], Gm(a.ln_g), Gm(a.ln_b),
-               a.fc2.b >= 0 ? Gm(a.fc2.b) : nullptr, a.fc1.b >= 0 ? Gm(a.fc1.b) : nullptr, R2));
+      MX(park(PARK_DAXIS_PARAMS, 2, [y = b.d.y, mean = b.d.mean, rstd = b.d.rstd, dz = gbuf[cur], dy = gbuf[i_dy], du = gbuf[i_du],
+                                     dgam = Gm(a.ln_g), dbet = Gm(a.ln_b), db2 = a.fc2.b >= 0 ? Gm(a.fc2.b) : nullptr,
+                                     db1 = a.fc1.b >= 0 ? Gm(a.fc1.b) : nullptr, R2](hipStream_t st) {
+        return daxis_param_grads(st, y, mean, rstd, dz, dy, du, dgam, dbet, db2, db1, R2);
+      }));
       { GemmDesc g = gemm_tn(gbuf[i_dy], od, b.d.h, hd, Gm(a.fc2.w), hd, od, hd, (int)R2); g.atomic = 1; MX(W_gemm(1, g)); }
       { GemmDesc g = gemm_tn(gbuf[i_dy], od, b.k.z, id, Gm(a.res), id, od, id, (int)R2); g.atomic = 1; MX(W_gemm(2, g)); }
       { GemmDesc g = gemm_tn(gbuf[i_du], hd, b.k.z, id, Gm(a.fc1.w), id, hd, id, (int)R2); g.atomic = 1; MX(W_gemm(3, g)); }
@@ -91,7 +67,6 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
       cur = i_dx;
     } else {
       const AxisW& a = w.ax[2];
-      const long R2 = (long)B * ol * ok;
       const float* xin = b.k.z;                              // residual / un-normalised input
       const float* xmlp = cfg.ln_first ? b.d.xn : b.k.z;     // what fc1 saw
       int i_dy = cur;
@@ -112,7 +87,7 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
       const float* dym = gbuf[i_dym];
       MX(W_fork(1, 2));                                      // weight gradients leave the critical path
       { GemmDesc g = gemm_tn(dym, od, b.d.h, hd, Gm(a.fc2.w), hd, od, hd, (int)R2); g.atomic = 1; MX(W_gemm(1, g)); }
-      if (a.fc2.b >= 0) MX(W_colsum(1, dym, R2, od, od, Gm(a.fc2.b)));
+      if (a.fc2.b >= 0) MX(park(PARK_COLSUM, 1, [dym, R2, od, db2 = Gm(a.fc2.b)](hipStream_t st) { return colsum(st, dym, R2, od, od, db2); }));
       if (a.res >= 0) { GemmDesc g = gemm_tn(dy, od, xin, id, Gm(a.res), id, od, id, (int)R2); g.atomic = 1; MX(W_gemm(2, g)); }
       GRAB(i_du);                                            // dU = (dYm . W2) * act'(U)
       { GemmDesc g = gemm_nn(dym, od, P(a.fc2.w), hd, gbuf[i_du], hd, (int)R2, hd, od); g.act = cfg.activation; g.gradact_u = b.d.u;
@@ -146,16 +121,10 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
     // ------------------------------------------------ K axis backward
     {
       const AxisW& a = w.ax[1];
-      KMixW kw;
-      std::memset(&kw, 0, sizeof kw);
-      kw.w1 = P(a.fc1.w); kw.b1 = a.fc1.b >= 0 ? P(a.fc1.b) : nullptr;
-      kw.w2 = P(a.fc2.w); kw.b2 = a.fc2.b >= 0 ? P(a.fc2.b) : nullptr;
-      kw.wr = a.res >= 0 ? P(a.res) : nullptr; kw.g = P(a.ln_g); kw.be = P(a.ln_b);
+      KMixW kw = kmix_w(i, pk);
       kw.dw1 = Gm(a.fc1.w); kw.db1 = a.fc1.b >= 0 ? Gm(a.fc1.b) : nullptr;
       kw.dw2 = Gm(a.fc2.w); kw.db2 = a.fc2.b >= 0 ? Gm(a.fc2.b) : nullptr;
       kw.dwr = a.res >= 0 ? Gm(a.res) : nullptr; kw.dg = Gm(a.ln_g); kw.dbe = Gm(a.ln_b);
-      kw.ik = ik; kw.hk = hk; kw.ok = ok; kw.act = cfg.activation; kw.ln_first = cfg.ln_first;
-      kw.drop_p = pk; kw.key = key(); kw.stream_id = 11 + 3 * i;
       GRAB(q);
       // K-axis parameter gradients: IN the chain kernel (MODE 0: data + parameter gradients; 0.99 ms at cfg2).  The split of round
       // 2a -- data gradient on the chain, the parameter-gradient reductions as a parked kernel beside the BPTT, 0.97 ms -- was NOT
@@ -169,9 +138,10 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
         static const int kdbg = dbg_env("MIMRL_DBG_KMIX") ? atoi(dbg_env("MIMRL_DBG_KMIX")) : 0;
         static const bool kmix_park = dbg_env("MIMRL_KMIX_PG_PARKED") != nullptr;   // debugging: the round-2a placement (not reproducible!)
         if (kmix_park) {
-          Deferred d{5, 2, GemmDesc(), b.l.z, (long)B * ol, id, 0, 0, nullptr};
-          d.p3 = gbuf[cur]; d.kw = kw; d.kw.dbg = kdbg;
-          deferred.push_back(d);
+          KMixW kp = kw; kp.dbg = kdbg;
+          MX(park(PARK_KMIX_PARAMS, 2, [x = b.l.z, dz = gbuf[cur], kp, R = (long)B * ol, id](hipStream_t st) {
+            return kmix_bwd_part(st, x, dz, nullptr, kp, R, id, 2);
+          }));
         } else {
           // The parameter gradients (same arithmetic recomputed) start RIGHT AWAY on side 3, beside the rest of the data-gradient chain,
           // and model_backward makes the BPTT wait for side 3: this kernel must never be resident next to gru_bwd_kernel -- beside it
@@ -188,11 +158,10 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
       cur = q;
     }
     // ------------------------------------------------ L axis backward (per-sample [.,C] tiles, C = ik*id)
-    if (bf16 && sw.fused_cube_bwd && !cfg.ln_first && pl <= 0.f && w.ax[0].res >= 0 && laxis_bwd_supported(il, hl, ol, ik * id) &&
+    if (bf16 && sw.fused_cube_bwd && !cfg.ln_first && pl <= 0.f && w.ax[0].res >= 0 && laxis_bwd_supported(il, hl, ol, (int)C) &&
         (il <= 64 || sw.laxis_bwd_long)) {   // (il > 64: the LONG instantiation, round 5b; MIMRL_LAXIS_BWD_LONG=0: the GEMM chain below)
       // one launch: LayerNorm(L) backward -> dY -> dU -> dX (+ LayerNorm and bias gradients); weight gradients stay GEMMs
       const AxisW& a = w.ax[0];
-      const long C = (long)ik * id;
       GRAB(i_dy); GRAB(i_du); GRAB(i_dx);
       LAxisBwdArgs fa;
       fa.dz = gbuf[cur]; fa.y = b.l.y; fa.mean = b.l.mean; fa.rstd = b.l.rstd; fa.gamma = P(a.ln_g); fa.u = b.l.u;
@@ -202,26 +171,17 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
       fa.B = B; fa.il = il; fa.hl = hl; fa.ol = ol; fa.C = (int)C; fa.act = cfg.activation;
       MX(laxis_bwd_fused(stream, fa));
       MX(W_fork(1, 3));
-      MX(W_lnpar(1, b.l.y, b.l.mean, b.l.rstd, gbuf[cur], Gm(a.ln_g), Gm(a.ln_b), B, ol, (int)C));
+      MX(park(PARK_LN_PARAMS, 1, [y = b.l.y, mean = b.l.mean, rstd = b.l.rstd, dz = gbuf[cur], dgam = Gm(a.ln_g), dbet = Gm(a.ln_b), B, ol,
+                                  C](hipStream_t st) { return colln_param_grads(st, y, mean, rstd, dz, dgam, dbet, B, ol, (int)C); }));
       release(cur);
-      { GemmDesc g; g.A = gbuf[i_dy]; g.sa_m = C; g.sa_k = 1; g.sa_b = (long)ol * C;        // dW2 += dY_b . H_b^T
-        g.B = b.l.h; g.sb_k = 1; g.sb_n = C; g.sb_b = (long)hl * C;
-        g.C = Gm(a.fc2.w); g.sc_m = hl; g.sc_n = 1; g.sc_b = 0; g.M = ol; g.N = hl; g.K = (int)C; g.batch = B; g.atomic = 1;
-        MX(W_gemm(1, g)); }
-      { GemmDesc g; g.A = gbuf[i_dy]; g.sa_m = C; g.sa_k = 1; g.sa_b = (long)ol * C;        // dWr += dY_b . X_b^T
-        g.B = xblk; g.sb_k = 1; g.sb_n = C; g.sb_b = (long)il * C;
-        g.C = Gm(a.res); g.sc_m = il; g.sc_n = 1; g.sc_b = 0; g.M = ol; g.N = il; g.K = (int)C; g.batch = B; g.atomic = 1;
-        MX(W_gemm(2, g)); }
-      { GemmDesc g; g.A = gbuf[i_du]; g.sa_m = C; g.sa_k = 1; g.sa_b = (long)hl * C;        // dW1 += dU_b . X_b^T
-        g.B = xblk; g.sb_k = 1; g.sb_n = C; g.sb_b = (long)il * C;
-        g.C = Gm(a.fc1.w); g.sc_m = il; g.sc_n = 1; g.sc_b = 0; g.M = hl; g.N = il; g.K = (int)C; g.batch = B; g.atomic = 1;
-        MX(W_gemm(3, g)); }
+      MX(W_gemm(1, gemm_lmul_dw(gbuf[i_dy], b.l.h, Gm(a.fc2.w), ol, hl, C, B)));   // dW2 += dY_b . H_b^T
+      MX(W_gemm(2, gemm_lmul_dw(gbuf[i_dy], xblk, Gm(a.res), ol, il, C, B)));      // dWr += dY_b . X_b^T
+      MX(W_gemm(3, gemm_lmul_dw(gbuf[i_du], xblk, Gm(a.fc1.w), hl, il, C, B)));    // dW1 += dU_b . X_b^T
       MX(W_join(1, 3));
       release(i_dy); release(i_du);
       cur = i_dx;
     } else {
       const AxisW& a = w.ax[0];
-      const long C = (long)ik * id;
       const float* xmlp = cfg.ln_first ? b.l.xn : xblk;
       int i_dy = cur;
       if (!cfg.ln_first) {
@@ -239,41 +199,25 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
         i_dym = q;
       }
       const float* dym = gbuf[i_dym];
-      // dW2[ol,hl] += sum_b dYm_b[ol,C] . H_b[hl,C]^T
+      auto W_rowsum = [&](int sd, const float* src, int rows, float* dst) -> int {   // bias gradients: dst[rows] += sums over samples and columns
+        return park(PARK_ROWSUM, sd, [src, B, rows, C, dst](hipStream_t st) { return rowsum_batched(st, src, B, rows, (int)C, dst); });
+      };
       MX(W_fork(1, 2));
-      { GemmDesc g; g.A = dym; g.sa_m = C; g.sa_k = 1; g.sa_b = (long)ol * C;
-        g.B = b.l.h; g.sb_k = 1; g.sb_n = C; g.sb_b = (long)hl * C;
-        g.C = Gm(a.fc2.w); g.sc_m = hl; g.sc_n = 1; g.sc_b = 0; g.M = ol; g.N = hl; g.K = (int)C; g.batch = B; g.atomic = 1;
-        MX(W_gemm(1, g)); }
-      if (a.fc2.b >= 0) MX(W_rowsum(1, dym, B, ol, (int)C, Gm(a.fc2.b)));
-      if (a.res >= 0) {
-        GemmDesc g; g.A = dy; g.sa_m = C; g.sa_k = 1; g.sa_b = (long)ol * C;
-        g.B = xblk; g.sb_k = 1; g.sb_n = C; g.sb_b = (long)il * C;
-        g.C = Gm(a.res); g.sc_m = il; g.sc_n = 1; g.sc_b = 0; g.M = ol; g.N = il; g.K = (int)C; g.batch = B; g.atomic = 1;
-        MX(W_gemm(2, g));
-      }
+      MX(W_gemm(1, gemm_lmul_dw(dym, b.l.h, Gm(a.fc2.w), ol, hl, C, B)));   // dW2[ol,hl] += sum_b dYm_b[ol,C] . H_b[hl,C]^T
+      if (a.fc2.b >= 0) MX(W_rowsum(1, dym, ol, Gm(a.fc2.b)));
+      if (a.res >= 0) MX(W_gemm(2, gemm_lmul_dw(dy, xblk, Gm(a.res), ol, il, C, B)));
       GRAB(i_du);                                            // dU_b[hl,C] = (W2^T . dYm_b) * act'(U)
-      { GemmDesc g; g.A = P(a.fc2.w); g.sa_m = 1; g.sa_k = hl; g.sa_b = 0;
-        if (bf16 && w2p[i] && w2p_valid[i] && hl % 4 != 0) { g.A = w2p[i]; g.sa_k = (hl + 3) & ~3; g.a_pad4 = 1; }
-        g.B = dym; g.sb_k = C; g.sb_n = 1; g.sb_b = (long)ol * C;
-        g.C = gbuf[i_du]; g.sc_m = C; g.sc_n = 1; g.sc_b = (long)hl * C; g.M = hl; g.N = (int)C; g.K = ol; g.batch = B;
+      { GemmDesc g = gemm_lmul_t(P(a.fc2.w), hl, dym, gbuf[i_du], hl, ol, C, B);
+        if (bf16 && w2p[i] && w2p_valid[i] && hl % 4 != 0) { g.A = w2p[i]; g.sa_k = s.hl_pad4(); g.a_pad4 = 1; }
         g.act = cfg.activation; g.gradact_u = b.l.u;
         MX(G_(g)); }
       MX(W_fork(3, 3));
-      { GemmDesc g; g.A = gbuf[i_du]; g.sa_m = C; g.sa_k = 1; g.sa_b = (long)hl * C;
-        g.B = xmlp; g.sb_k = 1; g.sb_n = C; g.sb_b = (long)il * C;
-        g.C = Gm(a.fc1.w); g.sc_m = il; g.sc_n = 1; g.sc_b = 0; g.M = hl; g.N = il; g.K = (int)C; g.batch = B; g.atomic = 1;
-        MX(W_gemm(3, g)); }
-      if (a.fc1.b >= 0) MX(W_rowsum(3, gbuf[i_du], B, hl, (int)C, Gm(a.fc1.b)));
+      MX(W_gemm(3, gemm_lmul_dw(gbuf[i_du], xmlp, Gm(a.fc1.w), hl, il, C, B)));
+      if (a.fc1.b >= 0) MX(W_rowsum(3, gbuf[i_du], hl, Gm(a.fc1.b)));
       GRAB(i_dx0);                                           // dX_b[il,C] = W1^T . dU_b (+LN-first bwd) + Wr^T . dY_b
       int i_dx = i_dx0;
-      { GemmDesc g; g.A = P(a.fc1.w); g.sa_m = 1; g.sa_k = il; g.sa_b = 0;
-        g.B = gbuf[i_du]; g.sb_k = C; g.sb_n = 1; g.sb_b = (long)hl * C;
-        g.C = gbuf[i_dx]; g.sc_m = C; g.sc_n = 1; g.sc_b = (long)il * C; g.M = il; g.N = (int)C; g.K = hl; g.batch = B;
-        if (a.res >= 0 && !cfg.ln_first) {                   // + Wr^T . dY_b in the same launch
-          g.A2 = P(a.res); g.sa2_m = 1; g.sa2_k = il; g.sa2_b = 0;
-          g.B2 = dy; g.sb2_k = C; g.sb2_n = 1; g.sb2_b = (long)ol * C; g.K2 = ol;
-        }
+      { GemmDesc g = gemm_lmul_t(P(a.fc1.w), il, gbuf[i_du], gbuf[i_dx], il, hl, C, B);
+        if (a.res >= 0 && !cfg.ln_first) gemm_lmul_t_add(g, P(a.res), dy, ol);   // + Wr^T . dY_b in the same launch
         MX(G_(g)); }
       if (cfg.ln_first) {
         MX(join(3, 3));                                      // dW1 / db1 on side 3 still read the dU buffer
@@ -286,9 +230,8 @@ int mimrl_handle::cube_backward(int cur_in, int* cur_out) {
       if (a.res >= 0 && !cfg.ln_first) {
         // fused above
       } else if (a.res >= 0) {
-        GemmDesc g; g.A = P(a.res); g.sa_m = 1; g.sa_k = il; g.sa_b = 0;
-        g.B = dy; g.sb_k = C; g.sb_n = 1; g.sb_b = (long)ol * C;
-        g.C = gbuf[i_dx]; g.sc_m = C; g.sc_n = 1; g.sc_b = (long)il * C; g.M = il; g.N = (int)C; g.K = ol; g.batch = B; g.beta = 1.f;
+        GemmDesc g = gemm_lmul_t(P(a.res), il, dy, gbuf[i_dx], il, ol, C, B);
+        g.beta = 1.f;
         MX(G_(g));
       } else {
         MX(add_inplace(stream, gbuf[i_dx], dy, (long)B * il * C));
@@ -339,27 +282,22 @@ int mimrl_handle::flush_deferred(int only_side) {
   // (RC,RC), the batch-reduced L-axis products (KC,KC).  Alone each is a ~20 us launch of 4..64 tiles.
   // (short sequences only: at T = 1000 the recurrence beside them runs for a millisecond, launch latencies are hidden and one
   // chip-filling launch in front of the BPTT costs more than it saves -- cfg5: 3.85 vs 3.74 ms)
-  const bool groupk = !prof_on && bf16 && !((dbg_skip_kinds >> 0) & 1) && cfg.seq_len <= 128;
+  const bool groupk = !prof_on && bf16 && !((dbg_skip_kinds >> PARK_GEMM) & 1) && cfg.seq_len <= 128;
   if (groupk) {
     std::vector<GemmDesc> cls[2];
-    for (const Deferred& d : deferred) if (d.kind == 0) cls[d.g.sa_k == 1 ? 0 : 1].push_back(d.g);
+    for (const Parked& d : deferred) if (d.kind == PARK_GEMM) cls[d.g.sa_k == 1 ? 0 : 1].push_back(d.g);
     for (int c = 0; c < 2; ++c) {
       hipStream_t st = only_side > 0 ? S(only_side) : S(1 + c % wg_sides);
       for (size_t i = 0; i < cls[c].size(); i += 12) MX(gemm_group_splitk(st, cls[c].data() + i, (int)std::min<size_t>(12, cls[c].size() - i), bf16));
     }
   }
   int rr = 2;
-  for (const Deferred& d : deferred) {
+  for (const Parked& d : deferred) {
     if ((dbg_skip_kinds >> d.kind) & 1) continue;
-    if (groupk && d.kind == 0) continue;
+    if (groupk && d.kind == PARK_GEMM) continue;
     static const bool dbg_defer_main = dbg_env("MIMRL_DBG_DEFER_MAIN") != nullptr;   // debugging: parked non-GEMM kernels on the main stream
     hipStream_t st = dbg_defer_main ? stream : only_side > 0 ? S(only_side) : S(1 + (groupk ? rr++ : d.side - 1) % wg_sides);
-    if (d.kind == 0) MX(G_on(st, d.g));
-    else if (d.kind == 1) MX(colsum(st, d.src, d.n0, (int)d.n1, (int)d.n2, d.dst));
-    else if (d.kind == 2) MX(rowsum_batched(st, d.src, (int)d.n0, (int)d.n1, (int)d.n2, d.dst));
-    else if (d.kind == 3) MX(colln_param_grads(st, d.src, d.p1, d.p2, d.p3, d.dst, d.dst2, (int)d.n0, (int)d.n1, (int)d.n2));
-    else if (d.kind == 6) MX(daxis_param_grads(st, d.src, d.p1, d.p2, d.p3, d.p4, d.p5, d.dst, d.dst2, d.dst3, d.dst4, d.n0));
-    else MX(kmix_bwd_part(st, d.src, d.p3, nullptr, d.kw, d.n0, (int)d.n1, 2));
+    MX(d.launch(st));
   }
   deferred.clear();
   return MIMRL_OK;
@@ -373,8 +311,8 @@ int mimrl_handle::model_backward() {
   DetDefer det_defer(stream, &det_ranges);   // deterministic build: one flush of the accumulation table at the end of the pass for everything that only feeds the gradient buckets
   const int B = cfg.batch, T = cfg.seq_len, L = cfg.time_len, D = cfg.d_common;
   const long BT_ = (long)B * T;
-  const int nb = cfg.n_blocks;
-  const int ol = cfg.d_outs[nb - 1][0], ok = cfg.d_outs[nb - 1][1], od = cfg.d_outs[nb - 1][2];
+  const BlockShape ls = shape(cfg.n_blocks - 1);
+  const int ol = ls.ol, ok = ls.ok, od = ls.od;
   // head backward -> gradient of the last cube output (in gbuf[0])
   MX(head_bwd(stream, dfeat, dpred, P(cls_w), bufs.feats, gbuf[0], Gm(cls_w), Gm(cls_b), B, ol, ok, od,
               cfg.compose_t_sum, cfg.compose_k_sum, head_gather_on ? &head_gather : nullptr, ncls()));

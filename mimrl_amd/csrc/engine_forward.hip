@@ -225,8 +225,8 @@ int mimrl_handle::model_forward(bool train, bool save, int knn_stage, int part) 
   // unless the backward pass needs it); likewise the head is the last block's epilogue when its rows fit one LDS tile (CubeHead)
   const int nbl = cfg.n_blocks;
   const bool fold_pre = sw.cube_bookends && fused_pre && !pre_done && part != 1 && D == 128 && T <= L && cube_block_fused(0, train);
-  const bool fold_head = sw.cube_bookends && part != 1 && cube_block_fused(nbl - 1, train) && cfg.d_outs[nbl - 1][0] * cfg.d_outs[nbl - 1][1] <= 64 &&
-                         cfg.d_outs[nbl - 1][2] == 128;
+  const BlockShape ls = shape(nbl - 1);
+  const bool fold_head = sw.cube_bookends && part != 1 && cube_block_fused(nbl - 1, train) && ls.ol * ls.ok <= 64 && ls.od == 128;
   if (part != 1 && T < L && !pre_done && !fold_pre) HIPX(hipMemsetAsync(cube0, 0, sizeof(float) * (size_t)B * L * 3 * D, stream));
   if (part != 2) {
     MX(fork(0, 5));
@@ -275,8 +275,8 @@ int mimrl_handle::model_forward(bool train, bool save, int knn_stage, int part) 
     }
   }
   // head (Model.py:489-515)
-  const BlockBuf& last = bb[cfg.n_blocks - 1];
-  const int ol = cfg.d_outs[cfg.n_blocks - 1][0], ok = cfg.d_outs[cfg.n_blocks - 1][1], od = cfg.d_outs[cfg.n_blocks - 1][2];
+  const BlockBuf& last = bb[nbl - 1];
+  const int ol = ls.ol, ok = ls.ok, od = ls.od;
   if (od != D) return set_error(MIMRL_ERR_ARG, "last block d_out must equal d_common (features feed 128-wide estimators)");
   CubeHead chead;
   chead.w = P(cls_w); chead.bias = P(cls_b); chead.ff = bufs.feats; chead.pred = bufs.pred; chead.C = ncls();
@@ -308,42 +308,34 @@ int mimrl_handle::dual_tail_pre() {
   return MIMRL_OK;
 }
 
-// whether block i takes the one-kernel path of cube_forward below (the same test, on the same chain of block shapes)
+// whether block i takes the one-kernel path of cube_forward below (the same test)
 bool mimrl_handle::cube_block_fused(int i, bool train) const {
   if (!bf16 || !sw.fused_cube || i < 0 || i >= cfg.n_blocks) return false;
-  int il = cfg.time_len, ik = 3, id = cfg.d_common;
-  for (int j = 0; j < i; ++j) { il = blk[j].ax[0].out; ik = blk[j].ax[1].out; id = blk[j].ax[2].out; }
-  const BlockW& w = blk[i];
+  const BlockShape s = shape(i);
   const float pmlp[3] = {train ? cfg.dropout_mlp[0] : 0.f, train ? cfg.dropout_mlp[1] : 0.f, train ? cfg.dropout_mlp[2] : 0.f};
-  return cube_fused_supported(il, w.ax[0].hid, w.ax[0].out, ik, w.ax[1].hid, w.ax[1].out, id, w.ax[2].hid, w.ax[2].out, cfg.ln_first != 0,
-                              cfg.res_project[i] != 0, cfg.bias != 0, pmlp);
+  return cube_fused_supported(s.il, s.hl, s.ol, s.ik, s.hk, s.ok, s.id, s.hd, s.od, cfg.ln_first != 0, cfg.res_project[i] != 0, cfg.bias != 0, pmlp);
 }
 
 int mimrl_handle::cube_forward(bool train, bool save, const CubePre* pre, const CubeHead* head) {
   const int B = cfg.batch;
   const float* x = cube0;
-  int il = cfg.time_len, ik = 3, id = cfg.d_common;
-  const bool no_fused = !sw.fused_cube;
   for (int i = 0; i < cfg.n_blocks; ++i) {
     const BlockW& w = blk[i];
     BlockBuf& b = bb[i];
-    const int hl = w.ax[0].hid, ol = w.ax[0].out, hk = w.ax[1].hid, ok = w.ax[1].out, hd = w.ax[2].hid, od = w.ax[2].out;
+    const BlockShape s = shape(i);
+    const int il = s.il, hl = s.hl, ol = s.ol, ik = s.ik, id = s.id, hd = s.hd, od = s.od;
     const float pl = train ? cfg.dropout_mlp[0] : 0.f, pk = train ? cfg.dropout_mlp[1] : 0.f,
                 pd = train ? cfg.dropout_mlp[2] : 0.f;
-    const float pmlp[3] = {pl, pk, pd};
     // bf16 mode: the whole block as ONE kernel with the sample tile resident in LDS (cube_fused.hip)
-    if (bf16 && !no_fused &&
-        cube_fused_supported(il, hl, ol, ik, hk, ok, id, hd, od, cfg.ln_first != 0, cfg.res_project[i] != 0, cfg.bias != 0, pmlp)) {
+    if (cube_block_fused(i, train)) {
       CubeFusedArgs fa;
       std::memset(&fa, 0, sizeof fa);
       auto PB = [&](long off) -> const float* { return off >= 0 ? P(off) : nullptr; };
       fa.x = x;
       fa.l_w1 = P(w.ax[0].fc1.w); fa.l_b1 = PB(w.ax[0].fc1.b); fa.l_w2 = P(w.ax[0].fc2.w); fa.l_b2 = PB(w.ax[0].fc2.b);
       fa.l_wr = P(w.ax[0].res); fa.l_g = P(w.ax[0].ln_g); fa.l_be = P(w.ax[0].ln_b);
-      fa.kw.w1 = P(w.ax[1].fc1.w); fa.kw.b1 = PB(w.ax[1].fc1.b); fa.kw.w2 = P(w.ax[1].fc2.w); fa.kw.b2 = PB(w.ax[1].fc2.b);
-      fa.kw.wr = P(w.ax[1].res); fa.kw.g = P(w.ax[1].ln_g); fa.kw.be = P(w.ax[1].ln_b);
-      fa.kw.ik = ik; fa.kw.hk = hk; fa.kw.ok = ok; fa.kw.act = cfg.activation; fa.kw.ln_first = 0; fa.kw.drop_p = 0.f;
-      fa.kw.key = key(); fa.kw.stream_id = 0;
+      fa.kw = kmix_w(i, 0.f);   // (a supported block has its residual projection and no LayerNorm in front: wr unconditionally)
+      fa.kw.wr = P(w.ax[1].res); fa.kw.ln_first = 0; fa.kw.stream_id = 0;
       fa.d_w1 = P(w.ax[2].fc1.w); fa.d_b1 = PB(w.ax[2].fc1.b); fa.d_w2 = P(w.ax[2].fc2.w); fa.d_b2 = PB(w.ax[2].fc2.b);
       fa.d_wr = P(w.ax[2].res); fa.d_g = P(w.ax[2].ln_g); fa.d_be = P(w.ax[2].ln_b);
       if (save) {
@@ -359,20 +351,19 @@ int mimrl_handle::cube_forward(bool train, bool save, const CubePre* pre, const 
       if (head && i == cfg.n_blocks - 1) { fa.head_on = 1; fa.head = *head; }
       MX(cube_block_fwd_fused(stream, fa));
       x = b.d.z;
-      il = ol; ik = ok; id = od;
       continue;
     }
     // ------------------------------------------------ L axis (MLPProcess.py:95-104 / 65-74)
     {
       const AxisW& a = w.ax[0];
-      const long C = (long)ik * id;
+      const long C = s.C();
       const float* xi = x;
       // round 5b, long sequences (the fused block kernel above needs L <= 64): one pass over the [L, C] slab of every sample instead of two
       // GEMM launches that each read it, a padded-copy launch and the LayerNorm launch (cfg3: 275 -> ~80 us per forward tail)
       const bool long_l = bf16 && sw.laxis_long && !cfg.ln_first && pl <= 0.f && a.res >= 0 && laxis_fwd_long_supported(il, hl, ol, (int)C);
       if (long_l) {
         if (w2p[i] && hl % 4 != 0) {   // (the padded fc2 copy is still what the backward's dU product reads)
-          MX(pad_rows(stream, P(a.fc2.w), w2p[i], ol, hl, (hl + 3) & ~3));
+          MX(pad_rows(stream, P(a.fc2.w), w2p[i], ol, hl, s.hl_pad4()));
           w2p_valid[i] = true;
         }
         LAxisLongArgs la;
@@ -383,37 +374,27 @@ int mimrl_handle::cube_forward(bool train, bool save, const CubePre* pre, const 
         MX(laxis_fwd_long(stream, la, sw.fwd_f16));
       } else {
       if (cfg.ln_first) { MX(colln_fwd(stream, x, P(a.ln_g), P(a.ln_b), b.l.xn, b.l.xn_mean, b.l.xn_rstd, B, il, (int)C)); xi = b.l.xn; }
-      GemmDesc g1;   // H = act(W1 . X_b + b1)
-      g1.A = P(a.fc1.w); g1.sa_m = il; g1.sa_k = 1; g1.sa_b = 0;
-      g1.B = xi; g1.sb_k = C; g1.sb_n = 1; g1.sb_b = (long)il * C;
-      g1.C = b.l.h; g1.sc_m = C; g1.sc_n = 1; g1.sc_b = (long)hl * C;
-      g1.M = hl; g1.N = (int)C; g1.K = il; g1.batch = B;
+      GemmDesc g1 = gemm_lmul(P(a.fc1.w), il, xi, b.l.h, hl, il, C, B);   // H = act(W1 . X_b + b1)
       g1.bias_m = a.fc1.b >= 0 ? P(a.fc1.b) : nullptr; g1.act = cfg.activation; g1.pre = b.l.u;
       g1.f16 = sw.fwd_f16;
       MX(G_(g1));
-      GemmDesc g2;   // Y = W2 . H_b + b2
-      g2.A = P(a.fc2.w); g2.sa_m = hl; g2.sa_k = 1;
-      if (bf16 && w2p[i] && hl % 4 != 0) {   // a 50-wide fc2 has 200-byte rows: without the padded copy this product (and dU in the
-        const int hp = (hl + 3) & ~3;        // backward pass) falls to the scalar-load kernel -- 0.2-0.27 ms each at cfg3
-        MX(pad_rows(stream, P(a.fc2.w), w2p[i], ol, hl, hp));
+      GemmDesc g2 = gemm_lmul(P(a.fc2.w), hl, b.l.h, b.l.y, ol, hl, C, B);   // Y = W2 . H_b + b2
+      // a 50-wide fc2 has 200-byte rows: without the padded copy this product (and dU in the backward pass) falls to the scalar-load
+      // kernel -- 0.2-0.27 ms each at cfg3
+      if (bf16 && w2p[i] && hl % 4 != 0) {
+        MX(pad_rows(stream, P(a.fc2.w), w2p[i], ol, hl, s.hl_pad4()));
         w2p_valid[i] = true;
-        g2.A = w2p[i]; g2.sa_m = hp; g2.a_pad4 = 1;
+        g2.A = w2p[i]; g2.sa_m = s.hl_pad4(); g2.a_pad4 = 1;
       }
-      g2.B = b.l.h; g2.sb_k = C; g2.sb_n = 1; g2.sb_b = (long)hl * C;
-      g2.C = b.l.y; g2.sc_m = C; g2.sc_n = 1; g2.sc_b = (long)ol * C;
-      g2.M = ol; g2.N = (int)C; g2.K = hl; g2.batch = B;
       g2.bias_m = a.fc2.b >= 0 ? P(a.fc2.b) : nullptr;
       const bool fuse_res = a.res >= 0 && pl <= 0.f;     // Y = W2.H + b2 + Wr.X in ONE launch (no dropout in between)
-      if (fuse_res) {
-        g2.A2 = P(a.res); g2.sa2_m = il; g2.sa2_k = 1; g2.sa2_b = 0;
-        g2.B2 = x; g2.sb2_k = C; g2.sb2_n = 1; g2.sb2_b = (long)il * C; g2.K2 = il;
-      }
+      if (fuse_res) gemm_lmul_add(g2, P(a.res), x, il);
       MX(G_(g2));
       if (!fuse_res) {
         MX(dropout_inplace(stream, b.l.y, (long)B * ol * C, pl, key(), 10 + 3 * i));
         if (a.res >= 0) {   // Y += Wr . X_b
-          GemmDesc g3 = g2;
-          g3.A = P(a.res); g3.sa_m = il; g3.B = x; g3.sb_b = (long)il * C; g3.K = il; g3.bias_m = nullptr; g3.beta = 1.f;
+          GemmDesc g3 = gemm_lmul(P(a.res), il, x, b.l.y, ol, il, C, B);
+          g3.beta = 1.f; g3.a_pad4 = g2.a_pad4;   // (the descriptor is a kernel argument: this launch carries the fc2 product's flag, which its own pitch il never needs)
           MX(G_(g3));
         } else {
           MX(add_inplace(stream, b.l.y, x, (long)B * ol * C));
@@ -423,21 +404,11 @@ int mimrl_handle::cube_forward(bool train, bool save, const CubePre* pre, const 
       }
     }
     // ------------------------------------------------ K axis (MLPProcess.py:106-112 / 76-82)
-    {
-      const AxisW& a = w.ax[1];
-      KMixW kw;
-      std::memset(&kw, 0, sizeof kw);
-      kw.w1 = P(a.fc1.w); kw.b1 = a.fc1.b >= 0 ? P(a.fc1.b) : nullptr;
-      kw.w2 = P(a.fc2.w); kw.b2 = a.fc2.b >= 0 ? P(a.fc2.b) : nullptr;
-      kw.wr = a.res >= 0 ? P(a.res) : nullptr; kw.g = P(a.ln_g); kw.be = P(a.ln_b);
-      kw.ik = ik; kw.hk = hk; kw.ok = ok; kw.act = cfg.activation; kw.ln_first = cfg.ln_first;
-      kw.drop_p = pk; kw.key = key(); kw.stream_id = 11 + 3 * i;
-      MX(kmix_fwd(stream, b.l.z, b.k.z, kw, (long)B * ol, id));
-    }
+    MX(kmix_fwd(stream, b.l.z, b.k.z, kmix_w(i, pk), (long)B * ol, id));
     // ------------------------------------------------ D axis (MLPProcess.py:114-120 / 84-90)
     {
       const AxisW& a = w.ax[2];
-      const long R2 = (long)B * ol * ok;
+      const long R2 = s.rows_d(B);
       const float* xi = b.k.z;
       if (cfg.ln_first) { MX(rowln_fwd(stream, b.k.z, P(a.ln_g), P(a.ln_b), b.d.xn, b.d.xn_mean, b.d.xn_rstd, R2, id)); xi = b.d.xn; }
       GemmDesc g1 = gemm_nt(xi, id, P(a.fc1.w), id, b.d.h, hd, (int)R2, hd, id);
@@ -463,7 +434,6 @@ int mimrl_handle::cube_forward(bool train, bool save, const CubePre* pre, const 
       if (!cfg.ln_first) MX(rowln_fwd(stream, b.d.y, P(a.ln_g), P(a.ln_b), b.d.z, b.d.mean, b.d.rstd, R2, od));
     }
     x = b.d.z;
-    il = ol; ik = ok; id = od;
   }
   return MIMRL_OK;
 }
@@ -475,14 +445,13 @@ int mimrl_handle::cube_forward(bool train, bool save, const CubePre* pre, const 
 // =================================================================================================
 // which blocks run the fused D-axis backward (needs bf16 operands in the backward section) + their transposed weight images
 int mimrl_handle::wt_images(hipStream_t st, bool bwd_bf16, bool launch, bool* d_fused) {
-  int din2 = cfg.d_common;
   WtTransposeArgs ta;
   ta.n = 0;
   for (int i = 0; i < cfg.n_blocks; ++i) {
     const AxisW& a = blk[i].ax[2];
+    const BlockShape s = shape(i);
     d_fused[i] = bwd_bf16 && sw.fused_cube_bwd && !cfg.ln_first && cfg.dropout_mlp[2] <= 0.f && a.res >= 0 &&
-                 daxis_bwd_supported(din2, a.hid, a.out) && ta.n + 3 <= 12;
-    din2 = cfg.d_outs[i][2];
+                 daxis_bwd_supported(s.id, s.hd, s.od) && ta.n + 3 <= 12;
     if (!d_fused[i]) continue;
     const long srcs[3] = {a.fc2.w, a.fc1.w, a.res};
     for (int q = 0; q < 3; ++q) { ta.src[ta.n] = P(srcs[q]); ta.dst[ta.n] = wtT[i][q]; ++ta.n; }

@@ -78,6 +78,35 @@ inline GemmDesc gemm_tn(const float* A, long lda, const float* Bm, long ldb, flo
   return d;
 }
 
+// ---- the L axis of CubeMLP: sample b is a row-major tile X_b[rows, C] (row pitch C, samples rows * C apart) that a weight matrix shared
+//      by all samples multiplies from the LEFT; batch = samples
+// Y_b[M, C] = W[M, K] . X_b[K, C], W row-major with row pitch ldw (>= K: the padded copy of a_pad4, which stays the caller's flag)
+inline GemmDesc gemm_lmul(const float* W, long ldw, const float* X, float* Y, int M, int K, long C, int batch) {
+  GemmDesc d; d.A = W; d.B = X; d.C = Y; d.M = M; d.N = (int)C; d.K = K; d.batch = batch;
+  d.sa_m = ldw; d.sa_k = 1; d.sb_k = C; d.sb_n = 1; d.sb_b = K * C; d.sc_m = C; d.sc_n = 1; d.sc_b = M * C;
+  return d;
+}
+// Y_b[M, C] = W^T . X_b[K, C], W stored [K, M] row-major with row pitch ldw   (data gradients: dU = W2^T . dY, dX = W1^T . dU)
+inline GemmDesc gemm_lmul_t(const float* W, long ldw, const float* X, float* Y, int M, int K, long C, int batch) {
+  GemmDesc d; d.A = W; d.B = X; d.C = Y; d.M = M; d.N = (int)C; d.K = K; d.batch = batch;
+  d.sa_m = 1; d.sa_k = ldw; d.sb_k = C; d.sb_n = 1; d.sb_b = K * C; d.sc_m = C; d.sc_n = 1; d.sc_b = M * C;
+  return d;
+}
+// dW[M, N] += sum_b dY_b[M, C] . X_b[N, C]^T   (weight gradients: the batch is one more reduction, float atomics into the one output)
+inline GemmDesc gemm_lmul_dw(const float* dY, const float* X, float* dW, int M, int N, long C, int batch) {
+  GemmDesc d; d.A = dY; d.B = X; d.C = dW; d.M = M; d.N = N; d.K = (int)C; d.batch = batch;
+  d.sa_m = C; d.sa_k = 1; d.sa_b = M * C; d.sb_k = 1; d.sb_n = C; d.sb_b = N * C; d.sc_m = N; d.sc_n = 1; d.sc_b = 0;
+  d.atomic = 1;
+  return d;
+}
+// the SECOND product of a gemm_lmul / gemm_lmul_t descriptor, + W2[M, K2] . X2_b[K2, C] resp. + W2[K2, M]^T . X2_b[K2, C] (W2 unpadded)
+inline void gemm_lmul_add(GemmDesc& d, const float* W2, const float* X2, int K2) {
+  d.A2 = W2; d.sa2_m = K2; d.sa2_k = 1; d.sa2_b = 0; d.B2 = X2; d.sb2_k = d.sb_k; d.sb2_n = 1; d.sb2_b = K2 * d.sb_k; d.K2 = K2;
+}
+inline void gemm_lmul_t_add(GemmDesc& d, const float* W2, const float* X2, int K2) {
+  d.A2 = W2; d.sa2_m = 1; d.sa2_k = d.M; d.sa2_b = 0; d.B2 = X2; d.sb2_k = d.sb_k; d.sb2_n = 1; d.sb2_b = K2 * d.sb_k; d.K2 = K2;
+}
+
 struct GemmPlan {
   int variant;        // 0 fp32 generic, 1 bf16 generic (BK 32), 2 bf16 lean BK 64, 3 bf16 lean BK 128, >= 10 fast path
   int fast, tm, tn;   // fast path: block tile (64*tm) x (64*tn)

@@ -638,7 +638,12 @@ def test_gradients_reproducible(workload, stage, graph):
     separable and concat critics, cfg3 (T = 500) and cfg5 (T = 1000) shapes.  Round 2b found the block-0 K-axis parameter gradients
     off by 5-30 % from run to run while their kernel ran beside the layer-1 BPTT (the structural fix keeps
     register-heavy kernels away from the recurrence, tests/test_codeobj.py pins the register facts it relies on) -- every parity test
-    passed at the time, because bf16-vs-fp32 bands are wider than that.  (tools/determinism.py is the same check as a CLI.)"""
+    passed at the time, because bf16-vs-fp32 bands are wider than that.  (tools/determinism.py is the same check as a CLI.)
+    KNOWN TO MISS its band: cfg2-concat-s2-graph.  Fresh engines land in two or three discrete result classes; between classes the layer-0
+    GRU input-weight gradients differ by 1.369e-4 (rnn_v.weight_ih_l0) and 1.017e-4 (rnn_a.weight_ih_l0_reverse) of the tensor's scale
+    against the 1e-4 band, every other tensor inside it.  Over all ordered triples of 18 fresh engines the assertion fails for 71-85 %;
+    the rate and both figures are the same with the CubeMLP host path before and after its refactor (shape(i), gemm_lmul*, Parked),
+    whose captured graph and deterministic results are identical.  The band stays."""
     runs, anchors = [], None
     for r in range(3):
         opt, N, batch, banks, eng = _bench_engine(workload, "bf16", graph, device_anchors=False)
